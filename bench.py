@@ -3,13 +3,16 @@
 — forward (HIP conv graph, bf16) + YOLOv5 loss + backward + clip + SGD-nesterov + EMA —
 batch 64 per GPU on synthetic COCO-shaped data resident in HBM, random-init weights.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL all-reduce of the flat gradient)
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step
+(--dump-outputs) and prints the line; `roofline` and `cpu_baseline` are null in it.  --full adds the measurements that take
+runs of their own:
   roofline     — dominant kernel family, algorithmic conv FLOPs / its measured duration (HIP events on the
                  launch stream, separate instrumented steps after the timed region)
   cpu_baseline — the oracle (torch-CPU fp32 port of the same train step) on a bounded sample, rank 0, N=1
+  decode_filter / nms_synthetic — (--workload infer) the fused decode + filter kernel and NMS on synthetic heads
 """
 import argparse
 import json
@@ -36,6 +39,95 @@ def make_hyp(dev, img, batch):
                 iou_loss_scale=0.05, cls_loss_scale=0.5, cof_loss_scale=1.0, anchor_match_thr=4.0,
                 class_smooth_factor=1.0, cls_pos_weight=1.0, cof_pos_weight=1.0,
                 loss_items_on_device=True)
+
+
+DUMP_BYTES = 60 << 20          # --dump-outputs: the arrays together (under 64 MB with the .npy headers)
+
+
+def step_outputs(out, model=None, ema=None):
+    """what a caller of the timed step receives from its last run, name -> array: the loss items of a train step (`loss_<key>`)
+    or the detections of an inference pass (`detections`: rows [image, x1, y1, x2, y2, conf, cls]; `detections_per_image`),
+    and the updated model / EMA state (`model_state`, `ema_state`: every floating-point tensor of the state dict, flattened
+    and concatenated in state-dict order)"""
+    arrays = {}
+    if "dets" in out:
+        dets = out["dets"]
+        rows = [np.concatenate([np.full((len(d), 1), i, np.float32), np.asarray(d, np.float32)], 1)
+                for i, d in enumerate(dets) if d is not None and len(d)]
+        arrays["detections"] = np.concatenate(rows) if rows else np.zeros((0, 7), np.float32)
+        arrays["detections_per_image"] = np.array([0 if d is None else len(d) for d in dets], np.float64)
+    else:
+        for k, v in out.items():
+            arrays["loss_" + k] = np.atleast_1d(np.asarray(v.detach().double().cpu() if torch.is_tensor(v) else v, np.float64))
+    for name, m in (("model_state", model), ("ema_state", None if ema is None else ema.ema)):
+        if m is not None:
+            arrays[name] = torch.cat([v.detach().reshape(-1).float() for v in m.state_dict().values() if v.is_floating_point()])
+    return arrays
+
+
+def write_outputs(path, arrays, budget=DUMP_BYTES, seed=0):
+    """`path`/<name>.npy for every array: float64 stays float64, everything else is written as float32.  When the arrays
+    together exceed `budget` bytes, the small ones are written whole and every array larger than an equal share of what they
+    leave is replaced by a fixed sample of that many elements (1-D): one element from each of as many equal strata of the
+    flattened array, drawn by a generator seeded from `seed` and the name, so the same arguments sample the same elements."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+
+    def width(a):
+        return 8 if a.dtype in (np.float64, torch.float64) else 4
+    numel = {k: (v.numel() if torch.is_tensor(v) else np.asarray(v).size) for k, v in arrays.items()}
+    order = sorted(arrays, key=lambda k: numel[k] * width(arrays[k]))
+    left = budget
+    for i, k in enumerate(order):
+        a = arrays[k]
+        w = width(a)
+        n = numel[k]
+        share = left // (len(order) - i)
+        if n * w > share:
+            m = max(1, share // w)
+            edges = (np.arange(m + 1, dtype=np.int64) * n) // m
+            rng = np.random.default_rng([seed, zlib.crc32(k.encode())])
+            idx = edges[:-1] + (rng.random(m) * (edges[1:] - edges[:-1])).astype(np.int64)
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)] if torch.is_tensor(a) else np.asarray(a).reshape(-1)[idx]
+            n = m
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        np.save(os.path.join(path, k + ".npy"), a.astype(np.float64 if w == 8 else np.float32, copy=False))
+        left -= n * w
+
+
+class StartState:
+    """the state one train step reads and updates — weights and float buffers (BatchNorm statistics), the EMA copy of both,
+    the momentum buffer and the loss's stage balances — as it was before the first step, restored by `restore()`.  The
+    weight gradients are summed with fp32 atomics: their last-bit differences flip the bf16 rounding of some weights, and two
+    runs of the same steps drift apart within a few steps.  The last timed step starts from this state, so that what it
+    computes (--dump-outputs) is the same in every run up to the rounding of one step; the copy costs one HBM pass over
+    ~120 MB (YOLOv5s) once per run."""
+
+    def __init__(self, model, opt, ema, lossf):
+        self.model, self.opt, self.ema, self.lossf = model, opt, ema, lossf
+        with torch.no_grad():
+            self.p0 = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).float().clone()
+            self.b0 = torch.cat([b.detach().reshape(-1) for b in model.buffers() if b.dtype == torch.float32]).clone()
+            init = getattr(lossf, "_init_balances", [])          # as the loss creates its balances at its first call
+            self.bal0 = torch.zeros(4, dtype=torch.float64)
+            self.bal0[:len(init)] = torch.tensor(init, dtype=torch.float64)
+            self.bal0 = self.bal0.to(self.p0.device)
+
+    def restore(self):
+        pack = self.model._yh_state()['pack']
+        fast = self.ema._fast
+        assert pack.flat.numel() == self.p0.numel() and fast is not None and fast[1].numel() == self.p0.numel()
+        with torch.no_grad():
+            pack.flat.copy_(self.p0)
+            fast[1].copy_(self.p0)
+            if pack.nbuf:
+                assert pack.fbuf.numel() >= self.b0.numel() and fast[2].numel() >= self.b0.numel()
+                pack.fbuf[:self.b0.numel()].copy_(self.b0)
+                fast[2][:self.b0.numel()].copy_(self.b0)
+            self.opt.buf.zero_()
+            bal = self.lossf._balances
+            if bal is not None:
+                bal.copy_(self.bal0)                    # device to device: the host never waits for the queue here
 
 
 def _host_threads():
@@ -116,6 +208,58 @@ def cpu_baseline(budget_s=14.0, batch=64, img=640):
                            f"head sets at {img}x{img} (~1 % of the anchors are candidates, {kept // nbatch} boxes kept per image), NumPy fp32 oracle"}}
 
 
+def _infer_extras(ev, dev, B, img):
+    """--full, --workload infer: the NMS of the evaluator and the fused decode + filter kernel, each timed on its own"""
+    from yoloseries_amd.utils.synth import synth_nms_heads
+    # a random-init net yields ~no detections: NMS throughput is measured on synthetic head tensors (SURVEY §8d):
+    # ~1 % of the anchors pass conf 0.001, 50 clusters of overlapping boxes per image
+    # all B images of the batch (VERDICT r04 #15), synthesised 16 at a time with a seed per chunk to bound the host memory
+    nb = B
+    heads = None
+    for c0 in range(0, nb, 16):
+        part = [torch.from_numpy(h).to(dev) for h in synth_nms_heads(min(16, nb - c0), img, 80, 3, seed=2 + c0 // 16, wh_shift=1.2)]
+        heads = part if heads is None else [torch.cat([a, b]) for a, b in zip(heads, part)]
+    for _ in range(2):
+        res = ev._nms_from_heads(heads)
+    torch.cuda.synchronize()
+    t0n = time.perf_counter()
+    reps = 10
+    for _ in range(reps):
+        res = ev._nms_from_heads(heads)
+    torch.cuda.synchronize()
+    dtn = (time.perf_counter() - t0n) / reps
+    kept = sum(0 if r is None else len(r) for r in res)
+    n_anchor = sum(3 * (img // s) ** 2 for s in (8, 16, 32))
+    ncand = sum(ev.last_ncand)
+    # the fused decode + candidate filter alone, against its algorithmic read (every head logit once: anchors x 85 x 2 B, SURVEY §8d)
+    import ctypes as C
+    from yoloseries_amd._lib import check, lib, stream_ptr
+    dd, canon, ptrs = ev._desc(heads)
+    capf = ((n_anchor + 3) // 4) * 4
+    candf = torch.empty(nb, capf, 6, dtype=torch.float32, device=dev)
+    ncf = torch.zeros(nb, dtype=torch.int32, device=dev)
+    dws = torch.empty(int(lib().yh_decode_filter_ws_bytes(C.byref(dd))), dtype=torch.uint8, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for it in range(reps + 1):
+        if it == 1:
+            e0.record()
+        check(lib().yh_decode_filter(C.byref(dd), ptrs, float(ev.conf_threshold), float(ev.cls_threshold), candf.data_ptr(),
+                                     ncf.data_ptr(), capf, dws.data_ptr(), stream_ptr()), "yh_decode_filter")
+    e1.record()
+    e1.synchronize()
+    df_ms = e0.elapsed_time(e1) / reps
+    df_bytes = nb * n_anchor * 85 * heads[0].element_size()
+    extra = {}
+    extra["decode_filter"] = {"bound": "hbm", "achieved": round(df_bytes / df_ms / 1e6, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": round(df_bytes / df_ms / 1e6 / HBM_PEAK_GBS, 4), "ms": round(df_ms, 3),
+                              "bytes_per_image": n_anchor * 85 * heads[0].element_size(), "images": nb}
+    extra["nms_synthetic"] = {"images": nb, "anchors_per_image": n_anchor, "candidates_per_image": round(ncand / nb, 1),
+                              "kept_boxes_per_image": round(kept / nb, 1), "images_per_s": round(nb / dtn, 1),
+                              "anchors_per_s": round(nb * n_anchor / dtn), "candidate_boxes_per_s": round(ncand / dtn),
+                              "kept_boxes_per_s": round(kept / dtn)}
+    return extra
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -123,11 +267,16 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="images per GPU")
     ap.add_argument("--img", type=int, default=640)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline, CPU baseline, decode / NMS extras (infer)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss items, model and EMA state; "
+                         "detections for --workload infer) as DIR/<name>.npy, float32 / float64, under 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--graph", action="store_true", help="capture the train step once into a hipGraph and replay it (utils/graph.py). "
                     "Off by default: measured on MI355X / ROCm 7.2 the replay is no faster than the eager two-stream schedule "
                     "(the step is bound by the ~700 dependent kernel boundaries, not by host launch time; DESIGN.md section 7)")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline steps")
     ap.add_argument("--model", default="small", choices=["small", "middle", "large", "xlarge"])
     ap.add_argument("--workload", default="train", choices=["train", "yolox", "infer"],
                     help="train: YOLOv5 train step (BASELINE configs[1], the default and the judged metric); yolox: YOLOXs + SimOTA "
@@ -166,6 +315,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     backend = os.environ.get("YH_DIST_BACKEND", "nccl")      # "gloo" only to rehearse N>1 without N GPUs
     if "WORLD_SIZE" in os.environ:
         if int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -232,7 +383,6 @@ def worker(args):
     if args.workload == "infer":
         # eval forward (BN folded, SiLU in the conv epilogue) + fused decode / filter / class-aware NMS; only kept rows cross PCIe
         from yoloseries_amd.trainer import YOLOV5Evaluator
-        from yoloseries_amd.utils.synth import synth_nms_heads
         model = cls(3, 80).to(dev).eval()
         ehyp = dict(device=dev, num_class=80, input_img_size=[img, img], iou_threshold=0.2, conf_threshold=0.3, cls_threshold=0.3,
                     max_predictions_per_img=300, iou_type="iou", mutil_label=False, agnostic=True, postprocess_bbox=True, wfb=False,
@@ -247,51 +397,8 @@ def worker(args):
         def step():
             return {"tot_loss": torch.zeros((), device=dev), "dets": ev(x)}
 
-        # a random-init net yields ~no detections: NMS throughput is measured on synthetic head tensors:
-        # ~1 % of the anchors pass conf 0.001, 50 clusters of overlapping boxes per image
-        # all B images of the batch, synthesised 16 at a time with a seed per chunk to bound the host memory
-        nb = B
-        heads = None
-        for c0 in range(0, nb, 16):
-            part = [torch.from_numpy(h).to(dev) for h in synth_nms_heads(min(16, nb - c0), img, 80, 3, seed=2 + c0 // 16, wh_shift=1.2)]
-            heads = part if heads is None else [torch.cat([a, b]) for a, b in zip(heads, part)]
-        for _ in range(2):
-            res = ev._nms_from_heads(heads)
-        torch.cuda.synchronize()
-        t0n = time.perf_counter()
-        reps = 10
-        for _ in range(reps):
-            res = ev._nms_from_heads(heads)
-        torch.cuda.synchronize()
-        dtn = (time.perf_counter() - t0n) / reps
-        kept = sum(0 if r is None else len(r) for r in res)
-        n_anchor = sum(3 * (img // s) ** 2 for s in (8, 16, 32))
-        ncand = sum(ev.last_ncand)
-        # the fused decode + candidate filter alone, against its algorithmic read (every head logit once: anchors x 85 x 2 B)
-        import ctypes as C
-        from yoloseries_amd._lib import check, lib, stream_ptr
-        dd, canon, ptrs = ev._desc(heads)
-        capf = ((n_anchor + 3) // 4) * 4
-        candf = torch.empty(nb, capf, 6, dtype=torch.float32, device=dev)
-        ncf = torch.zeros(nb, dtype=torch.int32, device=dev)
-        dws = torch.empty(int(lib().yh_decode_filter_ws_bytes(C.byref(dd))), dtype=torch.uint8, device=dev)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for it in range(reps + 1):
-            if it == 1:
-                e0.record()
-            check(lib().yh_decode_filter(C.byref(dd), ptrs, float(ev.conf_threshold), float(ev.cls_threshold), candf.data_ptr(),
-                                         ncf.data_ptr(), capf, dws.data_ptr(), stream_ptr()), "yh_decode_filter")
-        e1.record()
-        e1.synchronize()
-        df_ms = e0.elapsed_time(e1) / reps
-        df_bytes = nb * n_anchor * 85 * heads[0].element_size()
-        extra["decode_filter"] = {"bound": "hbm", "achieved": round(df_bytes / df_ms / 1e6, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                  "frac": round(df_bytes / df_ms / 1e6 / HBM_PEAK_GBS, 4), "ms": round(df_ms, 3),
-                                  "bytes_per_image": n_anchor * 85 * heads[0].element_size(), "images": nb}
-        extra["nms_synthetic"] = {"images": nb, "anchors_per_image": n_anchor, "candidates_per_image": round(ncand / nb, 1),
-                                  "kept_boxes_per_image": round(kept / nb, 1), "images_per_s": round(nb / dtn, 1),
-                                  "anchors_per_s": round(nb * n_anchor / dtn), "candidate_boxes_per_s": round(ncand / dtn),
-                                  "kept_boxes_per_s": round(kept / dtn)}
+        if args.full:
+            extra.update(_infer_extras(ev, dev, B, img))
     else:
         if args.workload == "yolox":
             from yoloseries_amd.loss import YOLOXLoss
@@ -342,12 +449,15 @@ def worker(args):
         from yoloseries_amd.utils.graph import GraphedStep
         stepper = GraphedStep(eager_step, pre_replay=[opt.graph_pre_replay, ema.graph_pre_replay], warmup=max(2, min(args.warmup, 3)))
         step = stepper
+    start = StartState(model, opt, ema, lossf) if args.workload != "infer" else None
     for _ in range(max(args.warmup, 4 if stepper is not None else 0)):
         out = step()
     sync_all()
     t0 = time.perf_counter()
     w0 = time.time()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if start is not None and i == args.steps - 1 and (i > 0 or args.warmup > 0):     # (no step yet: nothing to restore)
+            start.restore()                 # the last timed step: from the state before the first step (StartState)
         out = step()
     sync_all()
     dt = time.perf_counter() - t0
@@ -359,13 +469,16 @@ def worker(args):
         dt = tt.item()
     loss_val = float(out["tot_loss"].item())
     ips = world * B * args.steps / dt
+    if rank == 0 and args.dump_outputs:     # before any further step changes the weights
+        write_outputs(args.dump_outputs, step_outputs(out, None if args.workload == "infer" else model,
+                                                      None if args.workload == "infer" else ema))
 
     launch_mode = stepper.mode if stepper is not None else "eager"
     if stepper is not None and stepper.failed:
         print(f"# hipGraph capture failed, ran eagerly: {stepper.failed}", file=sys.stderr)
     step = eager_step                        # the instrumented roofline steps below time individual launches
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # rank 0 alone instruments a few extra steps: no gradient exchange in them (the other ranks wait below)
         if dp is not None:
             with dp.no_sync():
@@ -373,7 +486,7 @@ def worker(args):
         else:
             roof = measure_roofline(model, step, B)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "train" and args.model == "small":
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.workload == "train" and args.model == "small":
         try:
             cpu = cpu_baseline()
         except Exception as e:      # the oracle is test infrastructure; never let it fail the measurement

@@ -243,17 +243,16 @@ def test_driver_import_surface_resolves():
             exec(f"from {mod} import {', '.join(names)}", ns)
         exec("from models import *", ns)
         assert callable(ns["launch"]) and callable(ns["YOLOV5Small"])
-        # when the reference tree is present (build container), its own import statements are executed against the aliases
-        for ref in ("/root/reference/train_yolov5.py", "/root/reference/val_yolov5.py", "/root/reference/train_yolox.py",
-                    "/root/reference/val_yolox.py"):
-            if os.path.exists(ref):
-                import ast
-                tree = ast.parse(open(ref).read())
-                ours = set(DRIVER_IMPORTS)
-                for node in tree.body:
-                    if isinstance(node, ast.ImportFrom) and node.module in ours:
-                        code = ast.unparse(node)
-                        exec(code, {})           # raises ImportError if a name the reference's driver needs is missing
+        # the names each of the reference's four drivers imports from these roots, as recorded from their own
+        # `from <root> import ...` statements (tests/golden/driver_imports.json), resolved against the aliases
+        import json
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "driver_imports.json")) as f:
+            recorded = json.load(f)
+        assert sorted(recorded) == ["train_yolov5.py", "train_yolox.py", "val_yolov5.py", "val_yolox.py"]
+        for driver, roots in recorded.items():
+            assert roots and set(roots) <= set(DRIVER_IMPORTS), (driver, sorted(roots))
+            for mod, names in roots.items():
+                exec(f"from {mod} import {', '.join(names)}", {})   # raises ImportError if a name the driver needs is missing
     finally:
         _restore_modules(saved)
 

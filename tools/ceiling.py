@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Ceiling statement of a workload from its per-launch table (profiles/rNN_layers_*.txt, written by `YH_BENCH_LAYERS=N bench.py`):
+"""Ceiling statement of a workload from its per-launch table (profiles/rNN_layers_*.txt, written by `YH_BENCH_LAYERS=N bench.py --full`):
 per launch the time its ALGORITHMIC work needs on the achievable roofs — max(bytes / 5.5 TB/s, FLOP / 1.2 PFLOP/s): the HBM rate the
 streaming passes of this repo reach, and (as an upper bound for this design) a little under the best plain-HIP bf16 GEMM measured on this
 chip (MI355X_MICROARCH.md / cdna_hip_programming.md: 1.32-1.47 PFLOP/s on random data) — summed, against the measured kernel time; and the
