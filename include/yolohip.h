@@ -387,6 +387,10 @@ typedef struct yh_yolox_desc {
     int32_t topk; float center_radius;
     float   cls_cost_const;       /* class part of the SimOTA cost: constant in the reference (:111-147)        */
 } yh_yolox_desc;
+/* Ground truths per image: the assignment keeps at most 128 valid rows (class id >= 0) of an image in LDS.  `maxbox` may be
+ * larger (padding rows do not count), but the CALLER guarantees that no image has more than 128 valid rows: the library
+ * cannot see device data on the host, and rows beyond the 128th would be left out of the assignment.  YOLOXLoss
+ * (loss/yolox_loss.py) counts them whenever maxbox > 128 and raises YoloHipError before any launch. */
 size_t yh_yolox_saved_bytes(const yh_yolox_desc* d);
 size_t yh_yolox_ws_bytes(const yh_yolox_desc* d);
 int yh_yolox_layout(const yh_yolox_desc* d, int64_t* out8);

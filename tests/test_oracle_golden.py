@@ -306,3 +306,97 @@ def test_g14_evaluator_bbox_iou_and_do_nms_status():
     assert list(g["donms_status"]) == [0, -1, -1]
     outs = postproc.do_nms_v5(g["donms_dec"], 0.3, 0.3, 0.2)
     assert outs[0] is None and len(outs[1]) == 1 and len(outs[2]) >= 1
+
+
+# ---------------------------------------------------------------- G15 loss kernels' edge cases (both oracles on the wider domain)
+def _g15_names(kind):
+    from oracle import loss_cases as lc
+    g = lc.load()
+    return [str(n) for n in g["case_names"] if lc.spec_of(g, str(n))["kind"] == kind]
+
+
+def _g15_check_grads(g, key, grads, atol_rel):
+    for s, gr in enumerate(grads):
+        gn = gr.numpy()
+        if f"{key}_grad{s}" in g:
+            ref = g[f"{key}_grad{s}"]
+            assert gn.shape == ref.shape
+            np.testing.assert_allclose(gn, ref, rtol=1e-4, atol=atol_rel * np.abs(ref).max() + 1e-8)
+        else:
+            flat = gn.reshape(-1)
+            ref = g[f"{key}_gval{s}"]
+            np.testing.assert_allclose(flat[g[f"{key}_gidx{s}"]], ref, rtol=1e-4, atol=atol_rel * np.abs(ref).max() + 1e-9)
+            np.testing.assert_allclose([flat.astype(np.float64).sum(), np.abs(flat.astype(np.float64)).sum()], g[f"{key}_gsum{s}"], rtol=1e-5)
+
+
+@pytest.mark.parametrize("name", _g15_names("v5"))
+def test_g15_v5_loss_edges(name):
+    """V5LossOracle on every YOLOv5 case of g15 (empty images, stages without positives — NaN where the reference has it —
+    border boxes, duplicate cells, class counts, smoothing, pos-weights, focal parameters, scales, thresholds, four stages):
+    the bars of test_g3_loss"""
+    from oracle import loss_cases as lc
+    g = lc.load()
+    spec = lc.spec_of(g, name)
+    lf = v5loss.V5LossOracle(lc.anchors_of(spec), lc.hyp_of(spec, "cpu"), stage_num=spec["stages"])
+    for call, seed in enumerate(spec["seeds"]):
+        preds = [torch.from_numpy(h).requires_grad_(True) for h in lc.heads_of(spec, seed)]
+        out = lf(preds, g[f"{name}_c{call}_targets"])
+        vals = g[f"{name}_c{call}_vals"]
+        got = np.array([out["tot_loss"].item(), out["iou_loss"], out["cof_loss"], out["cls_loss"], out["tar_nums"]])
+        assert got[4] == vals[4]
+        lc.nan_equal_close(got, vals, rtol=2e-6, atol=1e-7)
+        np.testing.assert_allclose(lf.balances, g[f"{name}_c{call}_balances"], rtol=1e-7)
+        _g15_check_grads(g, f"{name}_c{call}", torch.autograd.grad(out["tot_loss"], preds), 0.0)
+
+
+@pytest.mark.parametrize("name", _g15_names("yolox"))
+def test_g15_yolox_loss_edges(name):
+    """YOLOXLossOracle (plain and with stable ties) on every YOLOX case of g15: foreground masks equal to the reference's,
+    items / balances / gradients with the bars of test_g8_yolox_loss"""
+    from oracle import loss_cases as lc
+    from oracle.yoloxloss import YOLOXLossOracle
+    g = lc.load()
+    spec = lc.spec_of(g, name)
+    for stable in (False, True):
+        lf = YOLOXLossOracle(lc.hyp_of(spec, "cpu"), stable_ties=stable)
+        for call, seed in enumerate(spec["seeds"]):
+            preds = {k: torch.from_numpy(v).requires_grad_(True) for k, v in lc.heads_of(spec, seed).items()}
+            t = torch.from_numpy(g[f"{name}_c{call}_targets"].copy())
+            out = lf(preds, t)
+            vals = g[f"{name}_c{call}_vals"]
+            got = np.array([out["tot_loss"].item(), out["iou_loss"], out["l1_loss"], out["cls_loss"], out["cof_loss"], out["fg_nums"], out["tar_nums"]])
+            assert got[5] == vals[5] and got[6] == vals[6]
+            np.testing.assert_allclose(got[:5], vals[:5], rtol=2e-6, atol=1e-7)
+            np.testing.assert_allclose(lf.balances, g[f"{name}_c{call}_balances"], rtol=1e-7)
+            np.testing.assert_array_equal(t.numpy(), g[f"{name}_c{call}_tars_after"])
+            for s, fg in enumerate(lf.last_fg):
+                np.testing.assert_array_equal(np.packbits(fg.numpy()), g[f"{name}_c{call}_fg{s}"])
+            _g15_check_grads(g, f"{name}_c{call}", torch.autograd.grad(out["tot_loss"], list(preds.values())), 1e-6)
+        if name == "x_radius025":
+            assert lf.counters["ctr_is_box"] > 0 and lf.counters["fallback"] == 0
+
+
+def test_g15_fallback_cells_and_counts():
+    """the oracle-only inputs whose seeds g15 fixes: the randperm-fallback targets are refused by the plain oracle and accepted
+    with `fallback_cells` naming one nearest cell per (stage, image) that needs it; the many-box inputs have the stated counts"""
+    from oracle import loss_cases as lc
+    from oracle.yoloxloss import YOLOXLossOracle
+    from yoloseries_amd.utils.synth import synth_yolox_heads
+    g = lc.load()
+    t0 = g["xo_fallback_targets"]
+    spec = dict(kind="yolox", img=128, B=2, hyp={})
+    heads = synth_yolox_heads(2, 128, 80, seed=int(g["xo_fallback_seed"][0]))
+    with pytest.raises(RuntimeError):
+        YOLOXLossOracle(lc.hyp_of(spec, "cpu"))({k: torch.from_numpy(v) for k, v in heads.items()}, torch.from_numpy(t0.copy()))
+    plan = lc.fallback_plan(t0, 128)
+    assert (2, 0) in plan and (2, 1) in plan and all(choose == 1 for _, choose in plan.values())
+    cells = {k: near[-1:] for k, (near, _) in plan.items()}
+    lf = YOLOXLossOracle(lc.hyp_of(spec, "cpu"), fallback_cells=cells)
+    preds = {k: torch.from_numpy(v).requires_grad_(True) for k, v in heads.items()}
+    out = lf(preds, torch.from_numpy(t0.copy()))
+    assert lf.counters["fallback"] == len(plan) and np.isfinite(out["tot_loss"].item())
+    for (st, b), c in cells.items():
+        n = (128 // (8, 16, 32)[st]) ** 2
+        assert lf.last_fg[st].numpy().reshape(2, n)[b].nonzero()[0].tolist() == c
+    for n in (16, 17, 128, 130):
+        assert int((g[f"xo_gt{n}_targets"][0, :, 4] >= 0).sum()) == n

@@ -92,6 +92,9 @@ def main():
     if sys.argv[1:] == ["--only", "g14"]:
         gen_g14(ref_models, ref_trainer)
         return
+    if sys.argv[1:] == ["--only", "g15"]:
+        gen_g15(ref_loss)
+        return
     from yoloseries_amd.utils.synth import COCO_ANCHORS, synth_head_outputs, synth_targets
 
     os.makedirs(OUT, exist_ok=True)
@@ -806,6 +809,277 @@ def gen_g14(ref_models, ref_trainer):
     g["donms_status"] = np.array(status)                   # 0: None, 1: rows stored, -1: the reference raised IndexError
     np.savez_compressed(os.path.join(OUT, "g14_round5.npz"), **g)
     print("g14 written", os.path.getsize(os.path.join(OUT, "g14_round5.npz")) / 1e6, "MB; reference do_nms status", status)
+
+
+def _g15_boxes(seed, B, img, nc, maxb, minb=1, lo=8.0, hi=None, empty=(), extra=None):
+    """(B, maxb, 6) xyxy targets like synth_targets, with a fixed row count, a side range of its own, images left without any
+    ground truth (`empty`) and an optional box appended to every non-empty image (`extra`, needs a free row)"""
+    rs = np.random.RandomState(seed)
+    hi = img / 2 if hi is None else hi
+    out = -np.ones((B, maxb, 6), np.float32)
+    for b in range(B):
+        n = rs.randint(minb, maxb + 1 - (extra is not None))
+        cx, cy = rs.uniform(0.1, 0.9, n) * img, rs.uniform(0.1, 0.9, n) * img
+        w, h = np.exp(rs.uniform(np.log(lo), np.log(hi), n)), np.exp(rs.uniform(np.log(lo), np.log(hi), n))
+        cl = rs.randint(0, nc, n)
+        if b in empty:
+            continue
+        out[b, :n, 0], out[b, :n, 2] = np.clip(cx - w / 2, 0, img), np.clip(cx + w / 2, 0, img)
+        out[b, :n, 1], out[b, :n, 3] = np.clip(cy - h / 2, 0, img), np.clip(cy + h / 2, 0, img)
+        out[b, :n, 4], out[b, :n, 5] = cl, b
+        if extra is not None:
+            out[b, n] = list(extra) + [(7 + b) % nc, b]
+    return out
+
+
+def _g15_border(img, big=False):
+    """hand-made border set, two images: boxes touching each edge and corner, the whole image, a 6 px box in the last cell,
+    centres at exactly k + 0.5 cells and exactly on a cell line (all three strides), centres within one cell of each edge"""
+    I = float(img)
+    k = 8.0 * (img // 16) + 4.0          # (k' + 0.5) cells of stride 8
+    m = 32.0 * max(img // 64, 1)         # on a cell line of strides 8, 16 and 32
+    a = [[0, 0.3 * I, 0.12 * I, 0.5 * I], [0.4 * I, 0, 0.6 * I, 0.1 * I], [0, 0, I, I], [0, 0, 0.1 * I, 0.12 * I],
+         [0.9 * I, 0.9 * I, I, I], [I - 6, I - 6, I, I], [k - 10, k - 10, k + 10, k + 10], [0, 0.5 * I - 10, 10, 0.5 * I + 10],
+         [0.5 * I - 10, 0, 0.5 * I + 10, 10], [12, 12, 28, 28]]
+    b = [[0.85 * I, 0.4 * I, I, 0.7 * I], [0.3 * I, 0.9 * I, 0.55 * I, I], [0.9 * I, 0, I, 0.1 * I], [0, 0.88 * I, 0.12 * I, I],
+         [m - 12, m - 12, m + 12, m + 12], [I - 10, 0.5 * I - 10, I, 0.5 * I + 10], [0.5 * I - 10, I - 10, 0.5 * I + 10, I],
+         [k - 6, m - 9, k + 6, m + 9]]
+    if big:
+        b.append([0.05 * I, 0.05 * I, 0.95 * I, 0.95 * I])
+    n = max(len(a), len(b)) + 1
+    out = -np.ones((2, n, 6), np.float32)
+    for i, rows in enumerate((a, b)):
+        for j, r in enumerate(rows):
+            out[i, j] = r + [(3 * j + i) % 80, i]
+    return out
+
+
+def gen_g15(ref_loss):
+    """G15: both training losses of the reference (loss/yolov5_loss.py, loss/yolox_loss.py) over hyper-parameter values and
+    target edge cases — images without ground truth, border boxes, duplicate cells, stages without positives, class counts
+    1..123, smoothing, pos-weights, focal parameters, scales, match thresholds, a fourth stage; SimOTA with every iou_type,
+    topk 1 / 17, centre radii 0.25 / 5.  Each case stores a JSON spec, its target arrays verbatim, and the reference's loss
+    items, counts, balances, foreground masks and gradients (whole where small, else sampled).  YOLOX seeds are searched here
+    (bounded) so that the reference does not enter its randperm fallback and the cost-tie rule decides nothing."""
+    import json
+    import torch
+    from oracle import loss_cases as lc
+    from oracle.yoloxloss import YOLOXLossOracle
+    from yoloseries_amd.utils.synth import synth_yolox_heads
+    torch.set_num_threads(8)
+    g, names = {}, []
+
+    def store_grads(key, grads):
+        for s, gr in enumerate(grads):
+            gn = gr.numpy()
+            assert np.isfinite(gn).all(), key
+            if gn.size <= 4096:
+                g[f"{key}_grad{s}"] = gn
+            else:
+                flat = gn.reshape(-1)
+                idx = lc.grad_sample(flat, s)
+                g[f"{key}_gidx{s}"], g[f"{key}_gval{s}"] = idx, flat[idx]
+                g[f"{key}_gsum{s}"] = np.array([flat.astype(np.float64).sum(), np.abs(flat.astype(np.float64)).sum()])
+
+    # ------------------------------------------------------------------ YOLOv5 loss
+    def v5(name, calls, fresh, img=128, B=2, stages=3, pscale=1.5, seed=1510, nan=False, **hyp):
+        spec = dict(kind="v5", img=img, B=B, stages=stages, pscale=pscale, hyp=hyp, seeds=[seed + 7 * k for k in range(len(calls))],
+                    fresh_seed=seed + 100)
+        h = lc.hyp_of(spec, "cpu")
+        lf = ref_loss.YOLOV5Loss(torch.from_numpy(lc.anchors_of(spec).copy()), h, stage_num=stages)
+        for k, t in enumerate(calls):
+            assert t.shape[0] == B
+            preds = [torch.from_numpy(x).requires_grad_(True) for x in lc.heads_of(spec, spec["seeds"][k])]
+            out = lf(preds, torch.from_numpy(t.copy()))
+            vals = np.array([out["tot_loss"].item(), out["iou_loss"], out["cof_loss"], out["cls_loss"], out["tar_nums"]], np.float64)
+            if k == len(calls) - 1 and nan is not None:
+                assert bool(np.isnan(vals).any()) == nan, (name, vals)          # a stage without positives: cls_loss is a mean of nothing
+            g[f"{name}_c{k}_targets"], g[f"{name}_c{k}_vals"] = t, vals
+            g[f"{name}_c{k}_balances"] = np.array(lf.balances, np.float64)
+            store_grads(f"{name}_c{k}", torch.autograd.grad(out["tot_loss"], preds))
+        g[f"{name}_f_targets"] = fresh
+        g[f"{name}_spec"] = np.array(json.dumps(spec, sort_keys=True))
+        names.append(name)
+        print(name, vals)
+
+    def std(seed, nc=80, **kw):
+        # one 90 x 70 box per image matches anchors of all three stages: no stage is left without positives by accident
+        kw.setdefault("extra", (20, 30, 110, 100))
+        return _g15_boxes(seed, kw.pop("B", 2), kw.pop("img", 128), nc, kw.pop("maxb", 6), **kw)
+    v5("t_empty_among", [std(1, B=4, empty=(1, 3))], std(2, B=4, empty=(0, 2)), B=4)
+    v5("t_all_empty_then_normal", [-np.ones((2, 6, 6), np.float32), std(3)], std(4, empty=(0, 1)))
+    v5("t_one_stage_only", [std(5, lo=5.0, hi=7.0, minb=2, extra=None)], std(6, lo=5.0, hi=7.0, minb=2, extra=None), nan=True)
+    for img in (640, 64):
+        v5(f"t_border_{img}", [_g15_border(img)], _g15_border(img), img=img, use_focal_loss=(img == 64), nan=None)
+    dup = -np.ones((2, 14, 6), np.float32)
+    for b in range(2):
+        for j in range(12 + 2 * b):
+            w, h = 12.0 + 9 * j, 110.0 - 8 * j
+            dup[b, j] = [70 - w / 2, 50 - h / 2, 70 + w / 2, 50 + h / 2, (5 * j + b) % 80, b]
+    v5("t_dup_cell", [dup], dup, nan=None)
+    v5("t_b1", [std(7, B=1)], std(8, B=1), B=1)
+    v5("t_b5", [std(9, B=5)], std(10, B=5), B=5)
+    v5("t_maxbox1", [std(11, B=4, maxb=1, extra=None)], std(12, B=4, maxb=1, extra=None), B=4, nan=None)
+
+    def sparse(B, mb, rows, seed):
+        src = _g15_boxes(seed, B, 64, 80, len(rows), minb=len(rows))
+        out = -np.ones((B, mb, 6), np.float32)
+        out[:, rows] = src
+        return out
+    v5("t_blk1024", [sparse(8, 128, [0, 1, 63, 64, 127], 13)], sparse(8, 128, [0, 5, 126, 127], 14), img=64, B=8, nan=None)     # 5*3*8*128 = 15 * 1024
+    v5("t_blk1025", [sparse(1, 751, [0, 400, 749, 750], 15)], sparse(1, 751, [1, 750], 16), img=64, B=1, nan=None)               # 5*3*751 = 11 * 1024 + 1
+    v5("h_default", [std(21)], std(22))
+    for nc in (1, 3, 20, 123):
+        v5(f"h_nc{nc}", [std(21, nc=nc)], std(22, nc=nc), num_class=nc)
+    v5("h_smooth09", [std(21)], std(22), class_smooth_factor=0.9)
+    v5("h_clspw2", [std(21)], std(22), cls_pos_weight=2.0)
+    v5("h_cofpw05", [std(21)], std(22), cof_pos_weight=0.5)
+    v5("h_focal_g2a05", [std(21)], std(22), focal_loss_gamma=2.0, focal_loss_alpha=0.5)
+    v5("h_focal_off", [std(21)], std(22), use_focal_loss=False)
+    v5("h_scales", [std(21)], std(22), iou_loss_scale=0.1, cls_loss_scale=0.7, cof_loss_scale=1.3)
+    v5("h_thr2", [std(21)], std(22), anchor_match_thr=2.0)
+    v5("h_thr8", [std(21)], std(22), anchor_match_thr=8.0)
+    big = dict(img=256, hi=200.0, extra=(8, 10, 250, 252))
+    v5("h_stage4", [std(23, **big), std(24, **big)], std(25, **big), img=256, stages=4)
+    v5("h_all", [std(26, nc=3, **big), std(27, nc=3, **big)], std(28, nc=3, **big), img=256, stages=4, num_class=3, class_smooth_factor=0.9,
+       cls_pos_weight=2.0, cof_pos_weight=0.5, focal_loss_gamma=2.0, focal_loss_alpha=0.5, iou_loss_scale=0.1, cls_loss_scale=0.7,
+       cof_loss_scale=1.3, anchor_match_thr=8.0)
+
+    # ------------------------------------------------------------------ YOLOX loss
+    class _Drew(Exception):
+        pass
+
+    def no_draw(*a, **k):
+        raise _Drew()
+
+    def x_ref(spec, calls, seeds):
+        """the reference on the calls of a case: per-call results, or None when it wants to draw at random"""
+        lf = ref_loss.YOLOXLoss(lc.hyp_of(spec, "cpu"))
+        masks = []
+        inner = lf.label_assign
+        lf.label_assign = lambda *a, **k: (lambda r: (masks.append(r[4].numpy().copy()), r)[1])(inner(*a, **k))
+        res = []
+        keep, torch.randperm = torch.randperm, no_draw
+        try:
+            for t, sd in zip(calls, seeds):
+                preds = {k: torch.from_numpy(v).requires_grad_(True) for k, v in lc.heads_of(spec, sd).items()}
+                tt = torch.from_numpy(t.copy())
+                out = lf(preds, tt)
+                grads = torch.autograd.grad(out["tot_loss"], list(preds.values()))
+                vals = np.array([out["tot_loss"].item(), out["iou_loss"], out["l1_loss"], out["cls_loss"], out["cof_loss"], out["fg_nums"], out["tar_nums"]], np.float64)
+                res.append((vals, np.array(lf.balances, np.float64), tt.numpy().copy(), masks[-3:], grads))
+        except _Drew:
+            return None
+        finally:
+            torch.randperm = keep
+        return res
+
+    def x_oracles(spec, calls, seeds, fallback_cells=None):
+        """stable-tie and plain oracle on the calls: (masks agree, stable oracle), or None when the oracle leaves its domain"""
+        h = lc.hyp_of(spec, "cpu")
+        oa, ob = YOLOXLossOracle(dict(h), stable_ties=True, fallback_cells=fallback_cells), YOLOXLossOracle(dict(h), fallback_cells=fallback_cells)
+        same, fgs = True, []
+        try:
+            for t, sd in zip(calls, seeds):
+                for o in (oa, ob):
+                    o({k: torch.from_numpy(v) for k, v in lc.heads_of(spec, sd).items()}, torch.from_numpy(t.copy()))
+                same = same and all(bool((a == b).all()) for a, b in zip(oa.last_fg, ob.last_fg))
+                fgs.append([m.numpy() for m in oa.last_fg])
+        except RuntimeError:
+            return None
+        return same, oa, fgs
+
+    def yx(name, make, ncalls=1, img=128, B=2, seed0=1600, want=None, **hyp):
+        """make(seed, call) -> targets; the seeds of the case and of the test's oracle-only repeat are searched from seed0"""
+        spec = dict(kind="yolox", img=img, B=B, hyp=hyp)
+        found = []
+        for seed in range(seed0, seed0 + 400):
+            calls = [make(seed, k) for k in range(ncalls)]
+            seeds = [seed + 1000 * (k + 1) for k in range(ncalls)]
+            o = x_oracles(spec, calls, seeds)
+            if o is None or not o[0]:
+                continue
+            if want is not None and not want(o[1]):
+                continue
+            if not found:
+                r = x_ref(spec, calls, seeds)
+                if r is None or not all(bool((a == b).all()) for rr, fg in zip(r, o[2]) for a, b in zip(rr[3], fg)):
+                    continue
+                found.append((seed, calls, r))
+            else:
+                found.append((seed, calls, None))
+                break
+        assert len(found) == 2, name
+        (seed, calls, r), (fseed, fcalls, _) = found
+        spec["seeds"], spec["fresh_seed"] = [seed + 1000 * (k + 1) for k in range(ncalls)], fseed + 1000 * ncalls
+        for k, (vals, bal, after, masks, grads) in enumerate(r):
+            g[f"{name}_c{k}_targets"], g[f"{name}_c{k}_vals"], g[f"{name}_c{k}_balances"] = calls[k], vals, bal
+            g[f"{name}_c{k}_tars_after"] = after
+            for s, mk in enumerate(masks):
+                g[f"{name}_c{k}_fg{s}"] = np.packbits(mk)
+            store_grads(f"{name}_c{k}", grads)
+        g[f"{name}_f_targets"] = fcalls[-1]
+        g[f"{name}_spec"] = np.array(json.dumps(spec, sort_keys=True))
+        names.append(name)
+        print(name, "seeds", seed, fseed, r[-1][0])
+
+    def xs(seed, k=0, nc=80, **kw):
+        kw.setdefault("lo", 40.0)
+        return _g15_boxes(seed + 50 * k, kw.pop("B", 2), kw.pop("img", 128), nc, kw.pop("maxb", 5), minb=kw.pop("minb", 2), **kw)
+    yx("x_default", xs)
+    yx("x_empty_among", lambda s, k: xs(s, B=4, empty=(1, 3) if s % 2 else (0, 2)), B=4)
+    yx("x_all_empty_then_normal", lambda s, k: -np.ones((2, 5, 6), np.float32) if k == 0 else xs(s), ncalls=2)
+    for img in (640, 64):
+        yx(f"x_border_{img}", lambda s, k, img=img: _g15_border(img, big=True), img=img)
+    yx("x_b1", lambda s, k: xs(s, B=1), B=1)
+    yx("x_maxbox1", lambda s, k: xs(s, B=4, maxb=1, minb=1), B=4)
+    yx("x_no_l1", xs, use_l1=False)
+    for nc in (1, 3, 20):
+        yx(f"x_nc{nc}", lambda s, k, nc=nc: xs(s, nc=nc), num_class=nc)
+    yx("x_smooth09", xs, class_smooth_factor=0.9)
+    yx("x_clspw2", xs, cls_pos_weight=2.0)
+    yx("x_cofpw05", xs, cof_pos_weight=0.5)
+    yx("x_scales", xs, iou_loss_scale=2.5, l1_loss_scale=0.5, cls_loss_scale=0.7, cof_loss_scale=1.3)
+    yx("x_focal_g2a05", xs, use_focal_loss=True, focal_loss_gamma=2.0, focal_loss_alpha=0.5)
+    yx("x_iou", xs, iou_type="iou")
+    yx("x_giou", xs, iou_type="giou")
+    yx("x_topk1", xs, topk=1)
+    yx("x_topk17_few", lambda s, k: xs(s, img=64, lo=36.0, hi=62.0), img=64, topk=17)          # 2 x 2 stride-32 map: 4 candidates at most
+    yx("x_radius025", xs, center_radius=0.25, want=lambda o: o.counters["ctr_is_box"] > 0)
+    yx("x_radius5", xs, center_radius=5)
+    yx("x_all", lambda s, k: xs(s, nc=3), num_class=3, use_l1=False, class_smooth_factor=0.9, cls_pos_weight=2.0, cof_pos_weight=0.5,
+       use_focal_loss=True, focal_loss_gamma=2.0, focal_loss_alpha=0.5, iou_type="giou", iou_loss_scale=2.5, cls_loss_scale=0.7,
+       cof_loss_scale=1.3, topk=5)
+
+    # ------------------------------------------------------------------ oracle-only YOLOX inputs: seeds fixed here
+    def many(seed, n):
+        """two 640^2 images: `n` valid boxes in the first (of n + 2 rows), six in the second"""
+        t = -np.ones((2, n + 2, 6), np.float32)
+        t[0, :n] = _g15_boxes(seed, 1, 640, 80, n, minb=n, lo=24.0, hi=200.0)[0]
+        t[1, :6] = _g15_boxes(seed + 1, 1, 640, 80, 6, minb=6, lo=24.0, hi=200.0)[0]
+        t[1, :6, 5] = 1
+        return t
+    spec640 = dict(kind="yolox", img=640, B=2, hyp={})
+    for n in (16, 17, 128, 130):
+        for seed in range(1700 + n, 1700 + n + 60):
+            o = x_oracles(spec640, [many(seed, n)], [seed + 1000])
+            if o is not None and o[0]:
+                break
+        else:
+            raise AssertionError(n)
+        g[f"xo_gt{n}_seed"] = np.array([seed, seed + 1000])
+        g[f"xo_gt{n}_targets"] = many(seed, n)
+        print("gt", n, "seed", seed)
+    # randperm fallback: 8-12 px boxes placed between the stride-32 cell centres (16 + 32 k) of a 128^2 image
+    fb = -np.ones((2, 3, 6), np.float32)
+    fb[0, :2] = [[27, 60, 37, 71, 4, 0], [90, 2, 98, 12, 9, 0]]
+    fb[1, :3] = [[58, 58, 70, 69, 1, 1], [0, 90, 9, 100, 2, 1], [100, 118, 112, 128, 3, 1]]
+    g["xo_fallback_targets"], g["xo_fallback_seed"] = fb, np.array([1790])
+    assert x_oracles(dict(kind="yolox", img=128, B=2, hyp={}), [fb], [1790]) is None            # the plain oracle refuses it
+    g["case_names"] = np.array(names)
+    path = os.path.join(OUT, "g15_loss_edges.npz")
+    np.savez_compressed(path, **g)
+    print("g15 written", os.path.getsize(path) / 1e3, "kB,", len(names), "cases")
 
 
 def gen_g10(ref_utils):

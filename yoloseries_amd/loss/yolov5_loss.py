@@ -198,8 +198,9 @@ class YOLOV5Loss:
         d = V5LossDesc()
         d.B, d.maxbox, d.num_class, d.num_anchor, d.num_stage = t.shape[0], t.shape[1], self.hyp['num_class'], len(self._anchors_host[0]), len(fm_sizes)
         d.img_size0, d.img_size1 = float(self.input_img_size[0]), float(self.input_img_size[1])
+        ld = ((d.num_anchor * (5 + d.num_class) + 7) // 8) * 8      # no prediction is read here; the descriptor check wants ld >= A*(5+nc)
         for s, (fh, fw) in enumerate(fm_sizes):
-            d.H[s], d.W[s], d.ldp[s] = fh, fw, 256
+            d.H[s], d.W[s], d.ldp[s] = fh, fw, ld
             for a in range(d.num_anchor):
                 d.anchors[(s * 3 + a) * 2], d.anchors[(s * 3 + a) * 2 + 1] = self._anchors_host[s][a]
         d.anchor_thr = float(self.hyp['anchor_match_thr'])

@@ -13,6 +13,7 @@ from ..layout import to_cell_major
 __all__ = ["YOLOXLoss"]
 
 _IOU_TYPES = {"iou": 0, "giou": 1, "ciou": 2}
+MAX_GT = 128          # ground truths per image the assignment kernel holds in LDS (MAXG in csrc/loss_yolox.hip, include/yolohip.h)
 
 
 def _canon5(p):
@@ -141,6 +142,13 @@ class YOLOXLoss:
         if not plist[0].is_cuda:
             raise _lib.YoloHipError("YOLOXLoss: predictions must live on an MI355X device (no CPU path in the product)")
         dev = plist[0].device
+        # a target tensor with more than MAX_GT rows may hold more valid boxes in one image than the kernel keeps: refused here,
+        # before any launch (tensors of up to MAX_GT rows cannot, and pay no host synchronisation for the check)
+        if tars.shape[1] > MAX_GT:
+            most = int((tars[..., 4] >= 0).sum(dim=1).max().item()) if tars.shape[0] else 0
+            if most > MAX_GT:
+                raise _lib.YoloHipError(f"YOLOXLoss: an image has {most} ground-truth boxes; at most {MAX_GT} per image are "
+                                        f"supported (MAXG in csrc/loss_yolox.hip)")
         b = tars[..., :4].clone()
         tars[..., 0:2] = (b[..., 0:2] + b[..., 2:4]) / 2
         tars[..., 2:4] = b[..., 2:4] - b[..., 0:2]
