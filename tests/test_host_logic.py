@@ -348,6 +348,31 @@ def test_planning_helpers_tolerate_empty_descriptors():
     assert lib().yh_conv_bnr_rows(C.byref(d)) == 0
 
 
+def test_conv_plan_table_is_stable():
+    """what yh_conv_igemm decides — kernel instantiation, BatchNorm partial-sum rows, fused-reduction rows — for every shipped entry of
+    the tuning table and 2 000 seeded random descriptors (invalid ones and their return codes included), through the C ABI alone,
+    against the record tests/golden/conv_plan_digest.json: one sha256 per 100 lines of the table and the set of kernel
+    instantiations (`tools/conv_plan_table.py --digest`, taken from the library as it was before the planner was consolidated
+    into conv_plan).  Planning is host code: no device needed.  A deliberate change of a plan — a new family, another tile —
+    regenerates the record; `tools/conv_plan_table.py --reduced` prints the lines of a chunk that differs"""
+    import importlib.util
+    import json
+    from yoloseries_amd._lib import lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("conv_plan_table", os.path.join(root, "tools", "conv_plan_table.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    want = json.load(open(os.path.join(root, "tests", "golden", "conv_plan_digest.json")))
+    got = mod.digest(mod.reduced(lib()), want["chunk"])
+    assert want["lines"] >= 2500 and got["lines"] == want["lines"]
+    assert got["names"] == want["names"], (sorted(set(got["names"]) - set(want["names"])), sorted(set(want["names"]) - set(got["names"])))
+    bad = [i for i, (g, w) in enumerate(zip(got["sha256"], want["sha256"])) if g != w]
+    assert not bad and len(got["sha256"]) == len(want["sha256"]), f"plans differ from the record in chunks {bad} (of {want['chunk']} lines each)"
+    fams = {n.split("<")[0] for n in want["names"]}
+    assert {"conv_stem_kernel", "conv_halo160_kernel", "conv_halo_kernel", "conv_v3_kernel", "conv_v2_kernel", "conv_igemm_kernel",
+            "conv_dg2_kernel", "conv_p3_kernel", "conv_pt_kernel"} <= fams, fams
+
+
 def test_executor_knows_every_program_entry_point():
     """yh_exec (csrc/exec.hip) replays the engine's command lists: every entry point a Program emits must be in its table, with
     the argument count the ctypes signature declares (stream included)"""

@@ -16,6 +16,7 @@
 // so every global store is a 16-byte row chunk, and optionally emits per-channel
 // sum / sum-of-squares partials (training-mode BatchNorm statistics) per block.
 #include "common.h"
+#include <initializer_list>
 #include <stdlib.h>
 
 #ifndef YH_CONV_ABLATE
@@ -2378,6 +2379,31 @@ int conv_dbg_mask() {
     static const int mask = [] { const char* e = getenv("YH_CONV_DBG"); return e ? atoi(e) : 0; }();
     return mask;
 }
+// YH_HALO_MAP (block order of the halo / LDS-DMA kernels), read once: -1 unset
+int conv_halo_map() {
+    static const int v = [] { const char* e = getenv("YH_HALO_MAP"); return e ? atoi(e) : -1; }();
+    return v;
+}
+
+// an epilogue beyond the plain store: affine / activation / residual / second destination (_na: accumulation aside)
+inline bool conv_generic_na(const yh_conv_desc* d) { return d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->nsplit < d->N; }
+inline bool conv_generic(const yh_conv_desc* d) { return conv_generic_na(d) || d->accumulate; }
+// epilogue of the v2 / v3 / halo kernels: 3 fused BatchNorm-backward reduction, 2 generic, 1 BatchNorm partial sums, 0 plain store
+inline int conv_epi(const yh_conv_desc* d) { return d->bnr_part ? 3 : (conv_generic(d) ? 2 : (d->stats ? 1 : 0)); }
+// stride-2 data gradient processed as four parity classes of output pixels (cls_slot)
+inline bool conv_cls(const yh_conv_desc* d) {
+    return d->mode == YH_CONV_DGRAD && d->stride == 2 && d->Ho % 2 == 0 && d->Wo % 2 == 0 && d->KH >= 2 && d->KW >= 2 && !d->stats;
+}
+// bytes a buffer descriptor of segment s / of the weights has to address (< 2 GiB for the buffer-load kernels)
+inline unsigned long conv_seg_bytes(const yh_conv_desc* d, int s) {
+    const yh_seg& g = d->seg[s];
+    const unsigned long npix = (unsigned long)d->B * (d->Hi >> g.ups) * (d->Wi >> g.ups);
+    return ((npix - 1) * g.ld + g.C) * 2;
+}
+inline int conv_ctot(const yh_conv_desc* d) { int c = 0; for (int s = 0; s < d->nseg; ++s) c += d->seg[s].C; return c; }
+inline unsigned long conv_w_bytes(const yh_conv_desc* d) { return (unsigned long)d->Npad * d->KH * d->KW * conv_ctot(d) * 2; }
+constexpr unsigned long GiB2 = 1ul << 31;
+
 bool stem_eligible(const yh_conv_desc* d)
 {
     if (d->mode != YH_CONV_FWD || d->nseg != 1 || d->seg[0].C != 16 || d->seg[0].ups) return false;
@@ -2402,7 +2428,7 @@ constexpr size_t conv_smem_bytes() {
     return (a > c ? a : c) + WM * 2 * BN * 4 + BM * 4;
 }
 
-// can this descriptor run on the buffer-load kernel (conv_v2_kernel)?  Shared by the grid planner and the launcher.
+// can this descriptor run on the buffer-load kernel (conv_v2_kernel)?
 // `rebased`: the caller re-bases its input descriptors at every tile of <= 256 output rows (conv_v3_kernel), so only the images
 // one tile spans have to fit the 2 GiB a descriptor addresses; otherwise the whole segment has to.
 static bool conv_buf_ok(const yh_conv_desc* d, bool rebased)
@@ -2410,31 +2436,50 @@ static bool conv_buf_ok(const yh_conv_desc* d, bool rebased)
     if (d->nseg < 1 || d->nseg > 2) return false;
     if (conv_dbg_mask() & 16) return false;
     if ((long)d->B * d->Hi * d->Wi >= (1L << 31) || (long)d->B * d->Ho * d->Wo >= (1L << 31)) return false;
-    int Ctot = 0;
     for (int s2 = 0; s2 < d->nseg; ++s2) {
         const yh_seg& g = d->seg[s2];
-        const unsigned long npix = (unsigned long)d->B * (d->Hi >> g.ups) * (d->Wi >> g.ups);
         if (!rebased) {
-            if (((npix - 1) * g.ld + g.C) * 2 >= (1ul << 31)) return false;  // buffer descriptors address < 2 GiB
+            if (conv_seg_bytes(d, s2) >= GiB2) return false;  // buffer descriptors address < 2 GiB
         } else {
             // a tile of 256 rows starts in image im0 and ends at most 256 / (rows per image) + 1 images later; the rows per
             // image are Ho*Wo, or a quarter of that for the parity classes of a stride-2 data gradient
             const unsigned long rows_img = (unsigned long)(d->Ho / 2 > 0 ? d->Ho / 2 : 1) * (d->Wo / 2 > 0 ? d->Wo / 2 : 1);
             const unsigned long span = 256 / rows_img + 2;
             const unsigned long pimg = (unsigned long)(d->Hi >> g.ups) * (d->Wi >> g.ups) * g.ld * 2;
-            if (span * pimg + 256ul * g.ld * 2 >= (1ul << 31)) return false;
+            if (span * pimg + 256ul * g.ld * 2 >= GiB2) return false;
         }
-        Ctot += g.C;
     }
-    if ((unsigned long)d->Npad * d->KH * d->KW * Ctot * 2 >= (1ul << 31)) return false;
-    const bool generic = d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->accumulate || d->nsplit < d->N;
-    if (generic && d->stats) return false;                                // statistics of an affine / activated output
+    if (conv_w_bytes(d) >= GiB2) return false;
+    if (conv_generic(d) && d->stats) return false;                        // statistics of an affine / activated output: generic kernel only
     return true;
 }
 bool conv_v2_ok(const yh_conv_desc* d) { return conv_buf_ok(d, false); }
 
-// output-channel tile (a 96-wide tile for the v5m / v5x widths was measured: +2 % on v5m training, -3 % on v5x inference)
+// ---- tile tables: the numbers of an instantiation are spelled here and nowhere else
+// register-staged kernels by output-channel tile (a 96-wide tile for the v5m / v5x widths was measured: +2 % on v5m training,
+// -3 % on v5x inference): waves and minimum waves per SIMD of conv_v2_kernel (wm2, wn2, minw2) and of conv_igemm_kernel (wm, wn, minw),
+// occ = resident blocks per CU of either
+struct ConvTile { int bn, wm2, wn2, minw2, wm, wn, minw, occ; };
+constexpr ConvTile CONV_TILES[3] = {
+    {32, 4, 1, 4, 4, 1, 4, 4},
+    {64, 4, 1, 3, 4, 1, 3, 3},           // (8 waves of 32 x 32 measured equal: LDS reads per MFMA double)
+    {128, 4, 2, 4, 2, 2, 2, 2},          // conv_v2_kernel: 8 waves: 4 per SIMD with two resident blocks, wave tile 32 x 64
+};
+constexpr ConvTile conv_tile(int bn) { return CONV_TILES[bn == 32 ? 0 : (bn == 64 ? 1 : 2)]; }
 int pick_bn(int N) { return N <= 32 ? 32 : (N <= 64 ? 64 : 128); }
+
+// LDS-DMA kernel (conv_v3_kernel) by variant: 1 = 256 x 128 tile (8 waves), 2 = 128 x 128 (4 waves), 3 = 128 x 64 (4 waves),
+// 4 = 256 x 256 (8 waves of 128 x 64: half the LDS-DMA bytes per MFMA of variant 1, whose 48 KB per k-step need 48 B/clk of the
+// CU's 64 B/clk intake at the full MFMA rate; 64-channel k-steps only).  stg / occ: ring stages and resident blocks per CU with
+// 64- / 32-channel k-steps
+struct V3Tile { int bmt, bn, wm, wn, stg64, stg32, occ64, occ32; };
+constexpr V3Tile V3_TILES[5] = {
+    {},
+    {256, 128, 4, 2, 3, 4, 1, 1},
+    {128, 128, 2, 2, 2, 4, 2, 2},
+    {128, 64, 2, 2, 3, 4, 2, 3},
+    {256, 256, 2, 4, 2, 0, 1, 1},
+};
 
 // channels per k-step: 64 (128-byte tile rows: whole cache lines per row, half the barriers) when every input
 // segment has a multiple of 64 channels (128-wide output tiles only), else 32
@@ -2448,79 +2493,62 @@ int pick_bkt(const yh_conv_desc* d, int bn) {
 }
 
 int conv_v3_bkt(const yh_conv_desc* d);
-// LDS-DMA kernel (conv_v3_kernel) variant for this descriptor: 0 = none (v2 / generic kernel), 1 = 256 x 128 tile (8 waves),
-// 2 = 128 x 128 (4 waves), 3 = 128 x 64 (4 waves), 4 = 256 x 256 (8 waves of 128 x 64: half the LDS-DMA bytes per MFMA of variant 1,
-// whose 48 KB per k-step need 48 B/clk of the CU's 64 B/clk intake at the full MFMA rate).
+// ---- eligibility of the families, asked in the order of conv_plan's chain (each assumes the earlier ones declined)
+// LDS-DMA kernel (conv_v3_kernel) variant for this descriptor (V3_TILES): 0 = none (v2 / generic kernel).
 // d->algo: 0 library default, 1 force v2, 2..4 = variant 1..3 when eligible, 14 = variant 4 when eligible.
 int conv_v3_variant(const yh_conv_desc* d)
 {
-    if (d->algo == 1 || d->algo == 5 || d->algo == 6 || stem_eligible(d) || !conv_buf_ok(d, true)) return 0;
+    if (d->algo == 1 || d->algo == 5 || d->algo == 6 || !conv_buf_ok(d, true)) return 0;
     if (conv_dbg_mask() & 512) return 0;
-    if (conv_v3_bkt(d) == 0) return 0;
+    const int bkt = conv_v3_bkt(d);
+    if (bkt == 0) return 0;
     if (d->N <= 32) return 0;
     if (d->tile_n == 32) return 0;
-    const bool generic = d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->accumulate || d->nsplit < d->N;
-    if (generic && d->stats) return 0;
-    if (d->algo >= 2 && d->algo <= 4) {
-        const int v = d->algo - 1;
-        return v;
-    }
+    if (d->algo >= 2 && d->algo <= 4) return d->algo - 1;
     if (d->algo == 14) {
         // 256 x 256 tile (variant 4): whole 64-channel blocks in every segment, N a multiple of 256, 64-channel k-steps; else the default
-        bool ok = conv_v3_bkt(d) == 64 && d->tile_k != 32 && d->N % 256 == 0;
+        bool ok = bkt == 64 && d->tile_k != 32 && d->N % 256 == 0;
         for (int s = 0; s < d->nseg; ++s) ok = ok && d->seg[s].C % 64 == 0;
         if (ok) return 4;
     }
     // default: the big tile for K-heavy layers with enough pixel tiles to fill the chip, else v2
     const long M = (long)d->B * d->Ho * d->Wo;
-    int Ctot = 0;
-    for (int s = 0; s < d->nseg; ++s) Ctot += d->seg[s].C;
-    const long K = (long)d->KH * d->KW * Ctot;
+    const long K = (long)d->KH * d->KW * conv_ctot(d);
     if (d->N > 64 && K >= 512 && M >= 256L * 192) return 1;
     return 0;
 }
-// halo kernel (conv_halo_kernel): 3x3 / stride 1 / pad 1, one input segment with >= 64 channels in a multiple of 16, N > 32.
+// what the two halo kernels share: 3x3 / stride 1 / pad 1 on one input segment that is not upsampled, on the buffer-load path
+bool conv_halo_shape_ok(const yh_conv_desc* d)
+{
+    if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->nseg != 1 || d->seg[0].ups) return false;
+    return d->Ho == d->Hi && d->Wo == d->Wi && conv_v2_ok(d);
+}
+// halo kernel (conv_halo_kernel): >= 64 input channels in a multiple of 16, N > 32.
 // d->algo: 5 forces it when eligible; 0 (library default) takes it when the tile geometry wastes < 25 % of the MFMA rows
 bool conv_halo_ok(const yh_conv_desc* d, HaloGeom* g)
 {
     if (d->algo != 0 && d->algo != 5) return false;
     if (conv_dbg_mask() & 1024) return false;
-    if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->nseg != 1 || d->seg[0].ups) return false;
     if (d->seg[0].C % 16 || d->seg[0].C < 64 || d->N <= 32 || d->tile_n == 32) return false;
-    if (d->Ho != d->Hi || d->Wo != d->Wi) return false;
-    if (!conv_v2_ok(d)) return false;
-    const bool generic = d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->accumulate || d->nsplit < d->N;
-    if (generic && d->stats) return false;
-    if ((long)d->B * d->Ho * d->Wo >= (1L << 31)) return false;
-    HaloGeom gg;
-    if (!conv_halo_geom(d->Ho, d->Wo, &gg)) return false;
+    if (!conv_halo_shape_ok(d) || !conv_halo_geom(d->Ho, d->Wo, g)) return false;
     if (d->algo == 0) {
-        const double eff = (double)d->Ho * d->Wo / ((double)gg.tiles_x * gg.tiles_y * 256.0);
-        if (eff < 0.75 || (long)d->B * gg.tiles_x * gg.tiles_y < 128) return false;
+        const double eff = (double)d->Ho * d->Wo / ((double)g->tiles_x * g->tiles_y * 256.0);
+        if (eff < 0.75 || (long)d->B * g->tiles_x * g->tiles_y < 128) return false;
     }
-    if (g) *g = gg;
     return true;
+}
+// 160-wide halo kernel (conv_halo160_kernel): only on request (d->algo == 6; the engine times it where it is eligible):
+// >= 64 input channels in a multiple of 32, N a multiple of 160, inference epilogues
+bool conv_halo160_ok(const yh_conv_desc* d, HaloGeom* g)
+{
+    if (d->algo != 6) return false;
+    if (d->seg[0].C % 32 || d->seg[0].C < 64 || d->N % 160 || d->stats || d->bnr_part) return false;
+    return conv_halo_shape_ok(d) && conv_halo_geom(d->Ho, d->Wo, g, YH_H160_ROWS == 328 ? 324 : YH_H160_ROWS);
 }
 
 // channels per k-step of the LDS-DMA kernel: 0 = not eligible.  64 needs whole 64-channel blocks in every segment but the
 // last, whose channel count may be any multiple of 16 (the "tail" variant of the kernel); 32 needs multiples of 32 everywhere.
 // Where both work, 64 is the default (half the barriers) and d->tile_k == 32 selects the short steps.
-// 160-wide halo kernel (conv_halo160_kernel): only on request (d->algo == 6; the engine times it where it is eligible):
-// 3x3 / stride 1 / pad 1, one segment with >= 64 channels in a multiple of 32, N a multiple of 160, inference epilogues
-bool conv_halo160_ok(const yh_conv_desc* d, HaloGeom* g)
-{
-    if (d->algo != 6 || stem_eligible(d)) return false;
-    if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->nseg != 1 || d->seg[0].ups) return false;
-    if (d->seg[0].C % 32 || d->seg[0].C < 64 || d->N % 160 || d->stats || d->bnr_part) return false;
-    if (d->Ho != d->Hi || d->Wo != d->Wi) return false;
-    if (!conv_v2_ok(d)) return false;
-    if ((long)d->B * d->Ho * d->Wo >= (1L << 31)) return false;
-    HaloGeom gg;
-    if (!conv_halo_geom(d->Ho, d->Wo, &gg, YH_H160_ROWS == 328 ? 324 : YH_H160_ROWS)) return false;
-    if (g) *g = gg;
-    return true;
-}
-
 int conv_v3_bkt(const yh_conv_desc* d) {
     bool ok64 = true, ok32 = true;
     int Ctot = 0;
@@ -2533,62 +2561,6 @@ int conv_v3_bkt(const yh_conv_desc* d) {
     if (Ctot < 64) ok64 = false;
     if (ok64 && !(ok32 && d->tile_k == 32)) return 64;
     return ok32 ? 32 : 0;
-}
-
-void conv_grid(const yh_conv_desc* d, int* gx, int* gy, int* bn) {
-    long M = (long)d->B * d->Ho * d->Wo;
-    if (stem_eligible(d)) {
-        const long blocks = (M / 32 + 3) / 4;
-        *gx = (int)(blocks < STEM_BLOCKS ? blocks : STEM_BLOCKS); *gy = 1; *bn = 32;
-        return;
-    }
-    HaloGeom hgm;
-    if (conv_halo160_ok(d, &hgm)) {
-        const int nt = d->N / 160;
-        const long ntiles = (long)d->B * hgm.tiles_x * hgm.tiles_y;
-        int cap = 256 / nt;
-        if (cap < 1) cap = 1;
-        if (d->grid_cap > 0) cap = d->grid_cap;
-        *gx = (int)(ntiles < cap ? ntiles : cap); *gy = nt; *bn = 160;
-        return;
-    }
-    if (!stem_eligible(d) && conv_halo_ok(d, &hgm)) {
-        const int b = d->N <= 64 ? 64 : 128;
-        const int nt = (d->N + b - 1) / b;
-        const long ntiles = (long)d->B * hgm.tiles_x * hgm.tiles_y;
-        int cap = 256 / nt;
-        if (cap < 1) cap = 1;
-        if (d->grid_cap > 0) cap = d->grid_cap;
-        *gx = (int)(ntiles < cap ? ntiles : cap); *gy = nt; *bn = b;
-        return;
-    }
-    if (const int v3 = conv_v3_variant(d)) {
-        const int bmt = (v3 == 1 || v3 == 4) ? 256 : 128;
-        const int b = v3 == 3 ? 64 : (v3 == 4 ? 256 : 128);
-        const int nt = (d->N + b - 1) / b;
-        const int bkt = conv_v3_bkt(d);
-        const int occ = (v3 == 1 || v3 == 4) ? 1 : (v3 == 2 ? 2 : (bkt == 64 ? 2 : 3));
-        const bool cls = d->mode == YH_CONV_DGRAD && d->stride == 2 && d->Ho % 2 == 0 && d->Wo % 2 == 0 && d->KH >= 2 && d->KW >= 2 && !d->stats;
-        const long Mc = cls ? M / 4 : M;
-        const int mt = (int)((Mc + bmt - 1) / bmt);
-        int cap = (256 * occ) / (nt * (cls ? d->KH * d->KW : 1));
-        if (cap < 1) cap = 1;
-        if (d->grid_cap > 0) cap = d->grid_cap;
-        *gx = mt < cap ? mt : cap; *gy = nt; *bn = b;
-        return;
-    }
-    int mtiles = (int)((M + BM - 1) / BM);
-    int b = (d->tile_n == 32 || d->tile_n == 64 || d->tile_n == 128) ? d->tile_n : pick_bn(d->N);
-    int nt = (d->N + b - 1) / b;
-    // persistent blocks: exactly one resident wave of blocks (256 CUs x blocks/CU of this instantiation), so there is
-    // no partially filled second round; also bounds the BatchNorm partial-sum rows the finalize kernel reduces
-    const int occ = pick_bkt(d, b) == 64 ? (b == 32 ? 3 : 2) : (b == 32 ? 4 : (b == 64 ? 3 : 2));
-    int cap = (256 * occ) / nt;
-    cap = (cap / 8) * 8;
-    if (cap < 8) cap = 8;
-    if (d->grid_cap > 0) cap = d->grid_cap;
-    int g = mtiles < cap ? mtiles : cap;
-    *gx = g; *gy = nt; *bn = b;
 }
 
 // Blocks per (parity class, slot) of a stride-2 data gradient on the register-staged / generic kernels.  The nine (class, slot)
@@ -2606,23 +2578,292 @@ int cls_blocks_per_slot(int gx_total, int zslots, long mtiles_cls)
     return g < 1 ? 1 : g;
 }
 
-}  // namespace
-
 // the planning helpers are called on half-filled descriptors (sizing, tuning): answer 0 instead of dividing by a zero dimension
-static bool conv_desc_plannable(const yh_conv_desc* d) {
+bool conv_desc_plannable(const yh_conv_desc* d) {
     return d && (d->nseg == 1 || d->nseg == 2) && d->B > 0 && d->Ho > 0 && d->Wo > 0 && d->Hi > 0 && d->Wi > 0 && d->KH > 0 && d->KW > 0 &&
            (d->stride == 1 || d->stride == 2) && d->N > 0 && d->seg[0].C > 0;
 }
-extern "C" int yh_conv_stat_blocks(const yh_conv_desc* d) {
-    if (!conv_desc_plannable(d)) return 0;
-    if (d->algo == 8) { const int r8 = yh_p3_rows(d); if (r8 > 0) return r8; }
-    if (d->algo == 13) { const int r13 = yh_pt_rows(d); if (r13 > 0) return r13; }
-    int gx, gy, bn;
-    conv_grid(d, &gx, &gy, &bn);
-    return gx;
+
+// ---- the plan: which instantiation runs for a descriptor, on what grid, writing how many partial-sum rows.  Made once per call
+// and read by the launcher, by yh_conv_kernel_name and by the two sizing entry points, so the four cannot drift apart.
+enum ConvFamily { FAM_STEM, FAM_HALO160, FAM_HALO, FAM_V3, FAM_V2, FAM_GENERIC };
+struct ConvPlan {
+    ConvFamily family;
+    int v3;                                          // FAM_V3: index into V3_TILES
+    int bmt, bn, wm, wn, minw, bkt, stg, epi, ntl;   // template arguments of the instantiation (those its family has)
+    bool tl;                                         // ragged last 64-channel block ("tail" forms of the halo / v3 kernels)
+    int gx, gy;                                      // persistent blocks over the pixel tiles x output-channel tiles
+    dim3 grid, block;                                // the launch made of them (parity-class slots in z, flattened rows)
+    int stat_rows, bnr_rows;                         // rows of the BatchNorm partial-sum slab / of the fused-reduction slab
+    HaloGeom geo;
+    ConvK k;
+};
+
+bool conv_plan(const yh_conv_desc* d, ConvPlan* pl)
+{
+    if (!conv_desc_plannable(d)) return false;
+    const long M = (long)d->B * d->Ho * d->Wo;
+    const bool cls = conv_cls(d), generic = conv_generic(d);
+    const long mtiles = ((cls ? M / 4 : M) + BM - 1) / BM;
+    ConvK& k = pl->k;
+    k.d = *d;
+    k.M = (int)(cls ? M / 4 : M);
+    k.Ctot = conv_ctot(d);
+    k.Ktot = d->KH * d->KW * k.Ctot;
+    k.nkt = (k.Ktot + BK - 1) / BK;
+    k.mtiles = (int)mtiles;
+    if (d->mode == YH_CONV_FWD) { k.sa = d->stride; k.sb = 1; k.sc = -d->pad; k.sdshift = 0; }
+    else { k.sa = 1; k.sb = -1; k.sc = d->pad; k.sdshift = d->stride == 2 ? 1 : 0; }
+    if (k.d.nsplit > k.d.N) k.d.nsplit = k.d.N + 8;   // everything goes to out0
+    if (d->nseg == 1) k.d.seg[1] = k.d.seg[0];
+    k.dbg = conv_dbg_mask();
+    k.cls = cls; k.Hc = cls ? d->Ho / 2 : d->Ho; k.Wc = cls ? d->Wo / 2 : d->Wo;
+    k.xgx = k.xgy = 0;
+    k.v2 = conv_v2_ok(d) ? 1 : 0;
+    k.pointwise = (d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && !cls) ? 1 : 0;
+    bool addressable = (unsigned long)M < GiB2 - BM && conv_w_bytes(d) < GiB2;        // by one descriptor per operand, not re-based
+    for (int s2 = 0; s2 < 2; ++s2) {
+        k.segbytes[s2] = 0; k.segbytes64[s2] = 0;
+        if (s2 < d->nseg) {
+            if (d->seg[s2].ups) k.pointwise = 0;
+            const unsigned long bytes = conv_seg_bytes(d, s2);
+            if (bytes >= GiB2) addressable = false;
+            k.segbytes[s2] = bytes >= GiB2 ? 0x7fffffffu : (unsigned)bytes;          // only read where k.v2 / halo hold
+            k.segbytes64[s2] = bytes;
+        }
+    }
+    if (d->nseg == 1) k.segbytes64[1] = k.segbytes64[0];
+    k.wbytes = (unsigned)conv_w_bytes(d);
+    // the buffer-load kernel walks 32-channel blocks: a first segment must end on a block boundary, the last may be ragged;
+    // the generic kernel's fast loader needs whole 32-channel blocks
+    k.fast = 1;
+    if (d->nseg > 1 && d->seg[0].C % 32) k.fast = 0;
+    if ((long)d->B * d->Hi * d->Wi >= (1L << 31)) k.fast = 0;
+    if (d->seg[d->nseg - 1].C % 32 && !k.v2) k.fast = 0;
+
+    // ---- family (one ordered chain), tile and persistent blocks gx x gy: exactly one resident wave of blocks (256 CUs x blocks/CU
+    // of the instantiation), so there is no partially filled second round; d->grid_cap overrides the cap on gx
+    pl->block = dim3(256);
+    pl->tl = false;
+    pl->v3 = 0;
+    long xtiles = mtiles;          // pixel tiles (halo: patches, stem: groups of four strips) the gx blocks walk
+    int cap, cap_min = 1;          // most blocks along x, the least the cap goes down to
+    if (stem_eligible(d)) {
+        pl->family = FAM_STEM;
+        pl->epi = d->scale ? 2 : (d->stats ? 1 : 0);
+        pl->ntl = (d->N + 31) / 32;
+        pl->bn = 32; pl->gy = 1;
+        xtiles = (M / 32 + 3) / 4;
+        cap = STEM_BLOCKS;
+    } else if (conv_halo160_ok(d, &pl->geo) || conv_halo_ok(d, &pl->geo)) {
+        pl->family = d->algo == 6 ? FAM_HALO160 : FAM_HALO;
+        pl->epi = pl->family == FAM_HALO160 ? (generic ? 2 : 0) : conv_epi(d);
+        pl->tl = (k.Ctot % 64) != 0;
+        pl->bn = pl->family == FAM_HALO160 ? 160 : (d->N <= 64 ? 64 : 128);
+        pl->gy = (d->N + pl->bn - 1) / pl->bn;
+        pl->block = dim3(512);
+        xtiles = (long)d->B * pl->geo.tiles_x * pl->geo.tiles_y;
+        cap = 256 / pl->gy;
+    } else if ((pl->v3 = conv_v3_variant(d)) != 0) {
+        const V3Tile& t = V3_TILES[pl->v3];
+        pl->family = FAM_V3;
+        pl->bkt = conv_v3_bkt(d);          // conv_v3_variant already checked the addressing (conv_buf_ok, re-based)
+        pl->bmt = t.bmt; pl->bn = t.bn; pl->wm = t.wm; pl->wn = t.wn;
+        pl->stg = pl->bkt == 64 ? t.stg64 : t.stg32;
+        pl->tl = pl->bkt == 64 && (k.Ctot % 64) != 0;
+        pl->epi = conv_epi(d);
+        pl->gy = (d->N + t.bn - 1) / t.bn;
+        pl->block = dim3(t.wm * t.wn * 64);
+        xtiles = ((cls ? M / 4 : M) + t.bmt - 1) / t.bmt;
+        cap = (256 * (pl->bkt == 64 ? t.occ64 : t.occ32)) / (pl->gy * (cls ? d->KH * d->KW : 1));
+    } else {
+        const ConvTile t = conv_tile((d->tile_n == 32 || d->tile_n == 64 || d->tile_n == 128) ? d->tile_n : pick_bn(d->N));
+        pl->family = k.v2 ? FAM_V2 : FAM_GENERIC;
+        pl->bn = t.bn;
+        pl->wm = k.v2 ? t.wm2 : t.wm; pl->wn = k.v2 ? t.wn2 : t.wn; pl->minw = k.v2 ? t.minw2 : t.minw;
+        pl->bkt = pick_bkt(d, t.bn);
+        pl->epi = conv_epi(d);
+        pl->gy = (d->N + t.bn - 1) / t.bn;
+        pl->block = dim3(pl->wm * pl->wn * 64);
+        xtiles = (M + BM - 1) / BM;          // (not per class: the cap below is what bounds a class launch)
+        // also bounds the BatchNorm partial-sum rows the finalize kernel reduces
+        cap = (256 * t.occ) / pl->gy / 8 * 8;
+        cap_min = 8;
+    }
+    if (cap < cap_min) cap = cap_min;
+    if (d->grid_cap > 0 && pl->family != FAM_STEM) cap = d->grid_cap;
+    const int gx = pl->gx = (int)(xtiles < cap ? xtiles : cap), gy = pl->gy;
+    pl->stat_rows = gx;          // (statistics exclude the parity classes: one row per gx block in every family)
+
+    // ---- the launch made of gx x gy, and the rows of the fused BatchNorm-backward reduction (one per block along x and z)
+    int rows = gx;
+    pl->grid = dim3(gx, gy, 1);
+    if (pl->family == FAM_STEM) {
+        // XCD-aware strip order (see the kernel): whole bands per XCD and whole workgroup octets; YH_STEM_MAP=0: strips in order
+        static const int smap = getenv("YH_STEM_MAP") ? atoi(getenv("YH_STEM_MAP")) : 1;
+        k.xgx = (smap && gx % 8 == 0 && ((long)d->B * d->Ho) % (8 * STEM_BAND) == 0) ? 1 : 0;
+        pl->grid = dim3(gx);
+    } else if (pl->family == FAM_HALO160 || pl->family == FAM_HALO) {
+        // conv_halo_kernel, measured (profiles/r04_step_experiments.txt j): +0.5 % on YOLOv5x inference, -1 % on the YOLOv5l train step
+        // (forward with statistics / data gradients) -> the XCD-major order only under the inference epilogue; YH_HALO_MAP=0: never
+        const bool xcd_major = pl->family == FAM_HALO160 || pl->epi == 2;
+        pl->geo.gx = gx; pl->geo.gy = gy; pl->geo.rowmajor = (conv_halo_map() == 0 || gy == 1 || !xcd_major) ? 1 : 0;
+        pl->geo.stamps = pl->family == FAM_HALO160 ? g_halo_stamps : nullptr;
+        pl->grid = dim3(gx * gy);              // one row of workgroups: halo_block_map
+    } else if (pl->family == FAM_V3) {
+        const int zslots = cls ? d->KH * d->KW : 1;      // (parity class, slot) pairs: see cls_slot
+        rows = gx * zslots;
+        pl->grid = dim3(gx, gy, zslots);
+        // one row of workgroups in XCD-major order, measured: no gain on YOLOv5x inference (707 / 712 -> 691 / 717 img/s), -2 % on the
+        // YOLOv5l train step: off (YH_HALO_MAP=2 enables it)
+        if (!cls && gy > 1 && conv_halo_map() == 2) { k.xgx = gx; k.xgy = gy; pl->grid = dim3(gx * gy, 1, 1); }
+    } else if (cls) {
+        // conv_v2_kernel walks the classes of a region inside the block where a class has enough regions: no z dimension.  The rows
+        // are conv_v2_kernel's, the only one of the two with the fused reduction (the generic kernel's launch refuses it)
+        const int zslots = d->KH * d->KW;
+        const int inner = cls_inner_blocks(gx < mtiles ? gx : (int)mtiles), per_slot = cls_blocks_per_slot(gx, zslots, mtiles);
+        const bool walk = mtiles >= CLS_INNER_MIN_TILES;
+        rows = walk ? inner : per_slot * zslots;
+        pl->grid = (walk && k.v2) ? dim3(inner, gy, 1) : dim3(per_slot, gy, zslots);
+    }
+    // 0: the descriptor cannot take the fused reduction here (the caller keeps the separate yh_bn_silu_bwd_reduce pass)
+    pl->bnr_rows = addressable ? rows : 0;
+    return true;
 }
 
-namespace {
+/* name of the instantiation, as profilers print it */
+void conv_plan_name(const ConvPlan& pl, char* out, int len)
+{
+    const char* tl = pl.tl ? "true" : "false";
+    switch (pl.family) {
+    case FAM_STEM: snprintf(out, len, "conv_stem_kernel<%d, %d>", pl.epi, pl.ntl); break;
+    case FAM_HALO160: snprintf(out, len, "conv_halo160_kernel<%d, %s>", pl.epi, tl); break;
+    case FAM_HALO: snprintf(out, len, "conv_halo_kernel<%d, %d, %s>", pl.bn, pl.epi, tl); break;
+    case FAM_V3: snprintf(out, len, "conv_v3_kernel<%d, %d, %d, %d, %d, %d, %d, %s>", pl.bmt, pl.bn, pl.wm, pl.wn, pl.bkt, pl.stg, pl.epi, tl); break;
+    case FAM_V2: snprintf(out, len, "conv_v2_kernel<%d, %d, %d, %d, %d, %d>", pl.bn, pl.wm, pl.wn, pl.minw, pl.epi, pl.bkt); break;
+    case FAM_GENERIC: snprintf(out, len, "conv_igemm_kernel<%d, %d, %d, %s, %d>", pl.bn, pl.wm, pl.wn, pl.k.fast ? "true" : "false", pl.minw); break;
+    }
+}
+
+// the dynamic-LDS limit of every epilogue form of an instantiation, once per device (YhDevOnce)
+inline void conv_set_lds(YhDevOnce& once, size_t sm, std::initializer_list<const void*> kernels)
+{
+    if (!once.need()) return;
+    for (const void* f : kernels) once.set(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+    once.done();
+}
+
+template <int NTL> void conv_launch_stem(const ConvPlan& pl, hipStream_t st)
+{
+    if (pl.epi == 2)      conv_stem_kernel<2, NTL><<<pl.grid, pl.block, 0, st>>>(pl.k);
+    else if (pl.epi == 1) conv_stem_kernel<1, (NTL <= 2 ? NTL : 2)><<<pl.grid, pl.block, 0, st>>>(pl.k);
+    else                  conv_stem_kernel<0, NTL><<<pl.grid, pl.block, 0, st>>>(pl.k);
+}
+void conv_launch_halo160(const ConvPlan& pl, hipStream_t st)
+{
+    const size_t sm = conv_halo160_smem_bytes();
+    static YhDevOnce attr_set;
+    conv_set_lds(attr_set, sm, {(const void*)conv_halo160_kernel<0, false>, (const void*)conv_halo160_kernel<0, true>,
+               (const void*)conv_halo160_kernel<2, false>, (const void*)conv_halo160_kernel<2, true>});
+    if (pl.epi == 2) { if (pl.tl) conv_halo160_kernel<2, true><<<pl.grid, pl.block, sm, st>>>(pl.k, pl.geo); else conv_halo160_kernel<2, false><<<pl.grid, pl.block, sm, st>>>(pl.k, pl.geo); }
+    else             { if (pl.tl) conv_halo160_kernel<0, true><<<pl.grid, pl.block, sm, st>>>(pl.k, pl.geo); else conv_halo160_kernel<0, false><<<pl.grid, pl.block, sm, st>>>(pl.k, pl.geo); }
+}
+template <int BN, bool TL> void conv_launch_halo(const ConvPlan& pl, hipStream_t st)
+{
+    const size_t sm = conv_halo_smem_bytes<BN>();
+    static YhDevOnce attr_set;
+    conv_set_lds(attr_set, sm, {(const void*)conv_halo_kernel<BN, 0, TL>, (const void*)conv_halo_kernel<BN, 1, TL>,
+               (const void*)conv_halo_kernel<BN, 2, TL>, (const void*)conv_halo_kernel<BN, 3, TL>});
+    if (pl.epi == 3)      conv_halo_kernel<BN, 3, TL><<<pl.grid, pl.block, sm, st>>>(pl.k, pl.geo);
+    else if (pl.epi == 2) conv_halo_kernel<BN, 2, TL><<<pl.grid, pl.block, sm, st>>>(pl.k, pl.geo);
+    else if (pl.epi == 1) conv_halo_kernel<BN, 1, TL><<<pl.grid, pl.block, sm, st>>>(pl.k, pl.geo);
+    else                  conv_halo_kernel<BN, 0, TL><<<pl.grid, pl.block, sm, st>>>(pl.k, pl.geo);
+}
+template <int V, int BKT, bool TL> void conv_launch_v3(const ConvPlan& pl, hipStream_t st)
+{
+    constexpr V3Tile T = V3_TILES[V];
+    constexpr int STG = BKT == 64 ? T.stg64 : T.stg32;
+    const size_t sm = conv3_smem_bytes<T.bmt, T.bn, T.wm, BKT, STG>();
+    static YhDevOnce attr_set;
+    conv_set_lds(attr_set, sm, {(const void*)conv_v3_kernel<T.bmt, T.bn, T.wm, T.wn, BKT, STG, 0, TL>, (const void*)conv_v3_kernel<T.bmt, T.bn, T.wm, T.wn, BKT, STG, 1, TL>,
+               (const void*)conv_v3_kernel<T.bmt, T.bn, T.wm, T.wn, BKT, STG, 2, TL>, (const void*)conv_v3_kernel<T.bmt, T.bn, T.wm, T.wn, BKT, STG, 3, TL>});
+    if (pl.epi == 3)      conv_v3_kernel<T.bmt, T.bn, T.wm, T.wn, BKT, STG, 3, TL><<<pl.grid, pl.block, sm, st>>>(pl.k);
+    else if (pl.epi == 2) conv_v3_kernel<T.bmt, T.bn, T.wm, T.wn, BKT, STG, 2, TL><<<pl.grid, pl.block, sm, st>>>(pl.k);
+    else if (pl.epi == 1) conv_v3_kernel<T.bmt, T.bn, T.wm, T.wn, BKT, STG, 1, TL><<<pl.grid, pl.block, sm, st>>>(pl.k);
+    else                  conv_v3_kernel<T.bmt, T.bn, T.wm, T.wn, BKT, STG, 0, TL><<<pl.grid, pl.block, sm, st>>>(pl.k);
+}
+template <int BN, int BKT> void conv_launch_v2(const ConvPlan& pl, hipStream_t st)
+{
+    constexpr ConvTile T = conv_tile(BN);
+    const size_t sm = conv_smem_bytes<BN, T.wm2, T.wn2, BKT>();
+    if (pl.epi == 3)      conv_v2_kernel<BN, T.wm2, T.wn2, T.minw2, 3, BKT><<<pl.grid, pl.block, sm, st>>>(pl.k);
+    else if (pl.epi == 2) conv_v2_kernel<BN, T.wm2, T.wn2, T.minw2, 2, BKT><<<pl.grid, pl.block, sm, st>>>(pl.k);
+    else if (pl.epi == 1) conv_v2_kernel<BN, T.wm2, T.wn2, T.minw2, 1, BKT><<<pl.grid, pl.block, sm, st>>>(pl.k);
+    else                  conv_v2_kernel<BN, T.wm2, T.wn2, T.minw2, 0, BKT><<<pl.grid, pl.block, sm, st>>>(pl.k);
+}
+template <int BN> void conv_launch_generic(const ConvPlan& pl, hipStream_t st)
+{
+    constexpr ConvTile T = conv_tile(BN);
+    const size_t sm = conv_smem_bytes<BN, T.wm, T.wn>();
+    if (pl.k.fast) conv_igemm_kernel<BN, T.wm, T.wn, true, T.minw><<<pl.grid, pl.block, sm, st>>>(pl.k);
+    else           conv_igemm_kernel<BN, T.wm, T.wn, false, T.minw><<<pl.grid, pl.block, sm, st>>>(pl.k);
+}
+
+int conv_launch(const ConvPlan& pl, hipStream_t st)
+{
+    static const char* const what[] = {"yh_conv_igemm(stem)", "yh_conv_igemm(halo160)", "yh_conv_igemm(halo)", "yh_conv_igemm(v3)", "yh_conv_igemm(v2)", "yh_conv_igemm"};
+    switch (pl.family) {
+    case FAM_STEM:
+        if (pl.ntl == 1) conv_launch_stem<1>(pl, st); else if (pl.ntl == 2) conv_launch_stem<2>(pl, st); else conv_launch_stem<3>(pl, st);
+        break;
+    case FAM_HALO160: conv_launch_halo160(pl, st); break;
+    case FAM_HALO:
+        if (pl.tl) { if (pl.bn == 64) conv_launch_halo<64, true>(pl, st); else conv_launch_halo<128, true>(pl, st); }
+        else       { if (pl.bn == 64) conv_launch_halo<64, false>(pl, st); else conv_launch_halo<128, false>(pl, st); }
+        break;
+    case FAM_V3:
+#define YH_V3_STEPS(V_) (pl.tl ? conv_launch_v3<V_, 64, true>(pl, st) : (pl.bkt == 64 ? conv_launch_v3<V_, 64, false>(pl, st) : conv_launch_v3<V_, 32, false>(pl, st)))
+        if (pl.v3 == 4) conv_launch_v3<4, 64, false>(pl, st); else if (pl.v3 == 1) YH_V3_STEPS(1); else if (pl.v3 == 2) YH_V3_STEPS(2); else YH_V3_STEPS(3);
+#undef YH_V3_STEPS
+        break;
+    case FAM_V2:
+        if (pl.bn == 128) { if (pl.bkt == 64) conv_launch_v2<128, 64>(pl, st); else conv_launch_v2<128, 32>(pl, st); }
+        else if (pl.bn == 64) conv_launch_v2<64, 32>(pl, st);
+        else conv_launch_v2<32, 32>(pl, st);
+        break;
+    case FAM_GENERIC:
+        if (pl.bn == 32) conv_launch_generic<32>(pl, st); else if (pl.bn == 64) conv_launch_generic<64>(pl, st); else conv_launch_generic<128>(pl, st);
+        break;
+    }
+    YH_CHECK_LAUNCH(what[pl.family]);
+    return YH_OK;
+}
+
+// ---- sibling families (own files, each with its own *_plan) behind d->algo: stride-2 data-gradient kernel (conv_dg2.hip), 3x3 patch
+// kernel (conv_p3.hip), 80-channel halo kernel (conv_h80.hip), pointwise kernels (conv_pw.hip, conv_pt.hip), 80 -> 160 kernel
+// (conv_c80.hip).  `who`: the entry points that hand the algo over (11 is unassigned: the launcher runs the default for it)
+enum { SIB_RUN = 1, SIB_STAT = 2, SIB_BNR = 4 };
+struct ConvSibling { int algo, who; int (*rows)(const yh_conv_desc*); int (*run)(const yh_conv_desc*, yh_stream, char*, int); };
+const ConvSibling CONV_SIBLINGS[] = {
+    {7, SIB_RUN | SIB_BNR, yh_dg2_rows, yh_dg2_run},           {8, SIB_RUN | SIB_STAT | SIB_BNR, yh_p3_rows, yh_p3_run},
+    {9, SIB_RUN, yh_h80_rows, yh_h80_run},                     {10, SIB_RUN, yh_pw_rows, yh_pw_run},
+    {11, SIB_RUN, nullptr, nullptr},                           {12, SIB_RUN, yh_c80_rows, yh_c80_run},
+    {13, SIB_RUN | SIB_STAT | SIB_BNR, yh_pt_rows, yh_pt_run},
+};
+// the sibling that takes the descriptor for entry point `who` (*rows: its grid rows), or nullptr.  Where the sibling of d->algo
+// declines, the library default (algo 0) plans instead: d then points to such a copy in *d0 — except for yh_conv_stat_blocks, which
+// has always gone on with the algo as it stands
+const ConvSibling* conv_sibling(const yh_conv_desc*& d, yh_conv_desc* d0, int who, int* rows)
+{
+    for (const ConvSibling& s : CONV_SIBLINGS)
+        if (s.algo == d->algo && (s.who & who)) {
+            if (s.rows && (*rows = s.rows(d)) > 0) return &s;
+            if (who != SIB_STAT) { *d0 = *d; d0->algo = 0; d = d0; }
+            break;
+        }
+    return nullptr;
+}
+
 // validates, plans and (name_out == nullptr) launches; with name_out only the instantiation's name is produced
 int conv_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len)
 {
@@ -2632,14 +2873,12 @@ int conv_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_l
     YH_CHECK_ARG(d->stride == 1 || d->stride == 2, "yh_conv_igemm: stride must be 1 or 2");
     YH_CHECK_ARG(d->B > 0 && d->Ho > 0 && d->Wo > 0 && d->Hi > 0 && d->Wi > 0, "yh_conv_igemm: bad dims");
     YH_CHECK_ARG(d->KH > 0 && d->KW > 0 && d->KH <= 7 && d->KW <= 7, "yh_conv_igemm: bad kernel size");
-    int Ctot = 0;
     for (int s = 0; s < d->nseg; ++s) {
         const yh_seg& g = d->seg[s];
         YH_CHECK_ARG(g.ptr && yh_aligned16(g.ptr), "yh_conv_igemm: seg %d pointer null/unaligned", s);
         YH_CHECK_ARG(g.C > 0 && g.C % 8 == 0 && g.ld % 8 == 0 && g.ld >= g.C, "yh_conv_igemm: seg %d C=%d ld=%d must be multiples of 8", s, g.C, g.ld);
         YH_CHECK_ARG(g.ups == 0 || g.ups == 1, "yh_conv_igemm: seg %d bad ups", s);
         if (g.ups) YH_CHECK_ARG(d->Hi % 2 == 0 && d->Wi % 2 == 0, "yh_conv_igemm: upsampled segment needs even Hi/Wi");
-        Ctot += g.C;
     }
     YH_CHECK_ARG(d->w && yh_aligned16(d->w), "yh_conv_igemm: weights null/unaligned");
     YH_CHECK_ARG(d->N > 0 && d->Npad >= d->N && d->Npad % 128 == 0, "yh_conv_igemm: N=%d Npad=%d (Npad must be a multiple of 128)", d->N, d->Npad);
@@ -2654,265 +2893,45 @@ int conv_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_l
         YH_CHECK_ARG((d->Ho + 2 * d->pad - d->KH) / d->stride + 1 == d->Hi && (d->Wo + 2 * d->pad - d->KW) / d->stride + 1 == d->Wi,
                      "yh_conv_igemm: dgrad geometry mismatch Ho=%d Hi=%d k=%d s=%d p=%d", d->Ho, d->Hi, d->KH, d->stride, d->pad);
     }
-    long M = (long)d->B * d->Ho * d->Wo;
-    YH_CHECK_ARG(M < (1L << 31) - BM, "yh_conv_igemm: too many output pixels");
-    if (d->algo >= 7 && d->algo <= 13) {      // stride-2 data-gradient kernel (conv_dg2.hip) / 3x3 patch kernel (conv_p3.hip) / 80-channel halo kernel (conv_h80.hip) /
-                                              // pointwise kernel (conv_pw.hip) where eligible, else the library default
-        if (d->algo == 7 && yh_dg2_rows(d) > 0) return yh_dg2_run(d, stream, name_out, name_len);
-        if (d->algo == 8 && yh_p3_rows(d) > 0) return yh_p3_run(d, stream, name_out, name_len);
-        if (d->algo == 9 && yh_h80_rows(d) > 0) return yh_h80_run(d, stream, name_out, name_len);
-        if (d->algo == 10 && yh_pw_rows(d) > 0) return yh_pw_run(d, stream, name_out, name_len);
-        if (d->algo == 12 && yh_c80_rows(d) > 0) return yh_c80_run(d, stream, name_out, name_len);
-        if (d->algo == 13 && yh_pt_rows(d) > 0) return yh_pt_run(d, stream, name_out, name_len);
-        yh_conv_desc d0 = *d;
-        d0.algo = 0;
-        return conv_run(&d0, stream, name_out, name_len);
-    }
+    YH_CHECK_ARG((long)d->B * d->Ho * d->Wo < (1L << 31) - BM, "yh_conv_igemm: too many output pixels");
+    yh_conv_desc d0;
+    int rows;
+    if (const ConvSibling* sib = conv_sibling(d, &d0, SIB_RUN, &rows)) return sib->run(d, stream, name_out, name_len);
 
-    ConvK k;
-    k.d = *d;
-    k.M = (int)M;
-    k.Ctot = Ctot;
-    k.Ktot = d->KH * d->KW * Ctot;
-    k.nkt = (k.Ktot + BK - 1) / BK;
-    k.mtiles = (int)((M + BM - 1) / BM);
-    if (d->mode == YH_CONV_FWD) { k.sa = d->stride; k.sb = 1; k.sc = -d->pad; k.sdshift = 0; }
-    else { k.sa = 1; k.sb = -1; k.sc = d->pad; k.sdshift = d->stride == 2 ? 1 : 0; }
-    if (k.d.nsplit > k.d.N) k.d.nsplit = k.d.N + 8;   // everything goes to out0
-    k.fast = 1;
-    k.dbg = conv_dbg_mask();
-    // the buffer-load kernel walks 32-channel blocks: a first segment must end on a block boundary, the last may be ragged
-    if (d->nseg > 1 && d->seg[0].C % 32) k.fast = 0;
-    const bool ragged = (d->seg[d->nseg - 1].C % 32) != 0;
-    if ((long)d->B * d->Hi * d->Wi >= (1L << 31)) k.fast = 0;
-    k.cls = 0; k.Hc = d->Ho; k.Wc = d->Wo;
-    if (d->mode == YH_CONV_DGRAD && d->stride == 2 && d->Ho % 2 == 0 && d->Wo % 2 == 0 && d->KH >= 2 && d->KW >= 2 && !d->stats) {
-        k.cls = 1; k.Hc = d->Ho / 2; k.Wc = d->Wo / 2;
-        k.M = (int)(M / 4);
-        k.mtiles = (k.M + BM - 1) / BM;
-    }
-
-    int gx, gy, bn;
-    conv_grid(d, &gx, &gy, &bn);
-    YH_CHECK_ARG(gy * bn <= d->Npad, "yh_conv_igemm: Npad too small for tile");
-    HaloGeom hgeo;
-    const bool halo160 = conv_halo160_ok(d, &hgeo);
-    const bool halo = !halo160 && !stem_eligible(d) && conv_halo_ok(d, &hgeo);
-    const int v3 = (halo || halo160) ? 0 : conv_v3_variant(d);
-    const int zslots = k.cls ? d->KH * d->KW : 1;      // (parity class, slot) pairs: see cls_slot
-    const int gx_all = gx < k.mtiles ? gx : k.mtiles;  // conv_v2_kernel walks the classes of a region inside the block: no z dimension
-    if (k.cls && !v3) gx = cls_blocks_per_slot(gx, zslots, k.mtiles);
-    dim3 grid(gx, gy, zslots), block(256);
-    // ---- lean buffer-load kernel
-    const int bkt = pick_bkt(d, bn);
-    k.v2 = conv_v2_ok(d) ? 1 : 0;
-    k.pointwise = (d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && !k.cls) ? 1 : 0;
-    for (int s2 = 0; s2 < 2; ++s2) {
-        k.segbytes[s2] = 0; k.segbytes64[s2] = 0;
-        if (s2 < d->nseg) {
-            const yh_seg& g = d->seg[s2];
-            if (g.ups) k.pointwise = 0;
-            const unsigned long npix = (unsigned long)d->B * (d->Hi >> g.ups) * (d->Wi >> g.ups);
-            const unsigned long bytes = ((npix - 1) * g.ld + g.C) * 2;
-            if (bytes >= (1ul << 31)) k.v2 = 0;
-            k.segbytes[s2] = bytes >= (1ul << 31) ? 0x7fffffffu : (unsigned)bytes;          // only read where k.v2 / halo hold
-            k.segbytes64[s2] = bytes;
-        }
-    }
-    if (d->nseg == 1) k.segbytes64[1] = k.segbytes64[0];
-    {
-        const unsigned long wb = (unsigned long)d->Npad * k.Ktot * 2;
-        if (wb >= (1ul << 31)) k.v2 = 0;
-        k.wbytes = (unsigned)wb;
-    }
-    if (d->nseg == 1) { k.d.seg[1] = k.d.seg[0]; }
-    if (stem_eligible(d)) {
-        const int epi = d->scale ? 2 : (d->stats ? 1 : 0);
-        const int ntl = (d->N + 31) / 32;
-        if (name_out) { snprintf(name_out, name_len, "conv_stem_kernel<%d, %d>", epi, ntl); return YH_OK; }
-        hipStream_t sst = (hipStream_t)stream;
-        const dim3 sg(gx), sb(256);
-        {   // XCD-aware strip order (see the kernel): whole bands per XCD and whole workgroup octets; YH_STEM_MAP=0: strips in order
-            static const int smap = getenv("YH_STEM_MAP") ? atoi(getenv("YH_STEM_MAP")) : 1;
-            const long rows = (long)d->B * d->Ho;
-            k.xgx = (smap && gx % 8 == 0 && rows % (8 * STEM_BAND) == 0) ? 1 : 0;
-        }
-#define YH_LAUNCH_STEM(NTL_)                                                            \
-        do {                                                                            \
-            if (epi == 2)      conv_stem_kernel<2, NTL_><<<sg, sb, 0, sst>>>(k);        \
-            else if (epi == 1) conv_stem_kernel<1, NTL_ <= 2 ? NTL_ : 2><<<sg, sb, 0, sst>>>(k); \
-            else               conv_stem_kernel<0, NTL_><<<sg, sb, 0, sst>>>(k);        \
-        } while (0)
-        if (ntl == 1) YH_LAUNCH_STEM(1); else if (ntl == 2) YH_LAUNCH_STEM(2); else YH_LAUNCH_STEM(3);
-#undef YH_LAUNCH_STEM
-        YH_CHECK_LAUNCH("yh_conv_igemm(stem)");
-        return YH_OK;
-    }
-    const bool generic = d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->accumulate || k.d.nsplit < d->N;
-    if (generic && d->stats) k.v2 = 0;            // statistics of an affine/activated output: generic kernel only
-    if (ragged && !k.v2) k.fast = 0;              // the generic kernel's fast loader needs whole 32-channel blocks
-    if (d->bnr_part) {
-        const bool generic_na = d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || k.d.nsplit < d->N;
-        YH_CHECK_ARG((k.v2 || v3) && !generic_na && !d->stats && d->mode == YH_CONV_DGRAD && !stem_eligible(d),
+    ConvPlan pl;
+    conv_plan(d, &pl);          // (plannable: checked above)
+    YH_CHECK_ARG(pl.gy * pl.bn <= d->Npad, "yh_conv_igemm: Npad too small for tile");
+    if (d->bnr_part && pl.family != FAM_STEM) {
+        YH_CHECK_ARG((pl.k.v2 || pl.family == FAM_V3) && !conv_generic_na(d) && !d->stats && d->mode == YH_CONV_DGRAD,
                      "yh_conv_igemm: the fused BatchNorm-backward reduction needs the plain buffer-load data-gradient path");
         YH_CHECK_ARG(d->bnr_z && yh_aligned16(d->bnr_z) && d->bnr_ldz % 8 == 0 && d->bnr_ws && d->bnr_C >= d->N && d->N % 8 == 0,
                      "yh_conv_igemm: bad fused-reduction operands");
     }
-    if (halo160) {
-        YH_CHECK_ARG(k.v2 && !k.cls, "yh_conv_igemm: the halo kernel needs the buffer-load path");
-        const int epi = generic ? 2 : 0;
-        const bool tl = (k.Ctot % 64) != 0;
-        if (name_out) { snprintf(name_out, name_len, tl ? "conv_halo160_kernel<%d, true>" : "conv_halo160_kernel<%d, false>", epi); return YH_OK; }
-        hipStream_t sth = (hipStream_t)stream;
-        static const int rowmajor = [] { const char* e = getenv("YH_HALO_MAP"); return (e && atoi(e) == 0) ? 1 : 0; }();
-        hgeo.gx = gx; hgeo.gy = gy; hgeo.rowmajor = (rowmajor || gy == 1) ? 1 : 0;
-        hgeo.stamps = g_halo_stamps;
-        const dim3 gridh(gx * gy), blkh(512);              // one row of workgroups: halo_block_map
-        const size_t sm = conv_halo160_smem_bytes();
-        static YhDevOnce attr_set;      
-        if (attr_set.need()) {
-            attr_set.set((const void*)conv_halo160_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-            attr_set.set((const void*)conv_halo160_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-            attr_set.set((const void*)conv_halo160_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-            attr_set.set((const void*)conv_halo160_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-            attr_set.done(); 
-        }
-        if (epi == 2) { if (tl) conv_halo160_kernel<2, true><<<gridh, blkh, sm, sth>>>(k, hgeo); else conv_halo160_kernel<2, false><<<gridh, blkh, sm, sth>>>(k, hgeo); }
-        else          { if (tl) conv_halo160_kernel<0, true><<<gridh, blkh, sm, sth>>>(k, hgeo); else conv_halo160_kernel<0, false><<<gridh, blkh, sm, sth>>>(k, hgeo); }
-        YH_CHECK_LAUNCH("yh_conv_igemm(halo160)");
-        return YH_OK;
-    }
-    if (halo) {
-        YH_CHECK_ARG(k.v2 && !k.cls, "yh_conv_igemm: the halo kernel needs the buffer-load path");
-        const int epi = d->bnr_part ? 3 : (generic ? 2 : (d->stats ? 1 : 0));
-        const bool tl = (k.Ctot % 64) != 0;
-        if (name_out) { snprintf(name_out, name_len, tl ? "conv_halo_kernel<%d, %d, true>" : "conv_halo_kernel<%d, %d, false>", bn, epi); return YH_OK; }
-        hipStream_t sth = (hipStream_t)stream;
-        // measured (profiles/r04_step_experiments.txt j): +0.5 % on YOLOv5x inference, -1 % on the YOLOv5l train step (forward with
-        // statistics / data gradients) -> the XCD-major order only under the inference epilogue
-        static const int rowmajor = [] { const char* e = getenv("YH_HALO_MAP"); return (e && atoi(e) == 0) ? 1 : 0; }();
-        hgeo.gx = gx; hgeo.gy = gy; hgeo.rowmajor = (rowmajor || gy == 1 || epi != 2) ? 1 : 0;
-        hgeo.stamps = nullptr;
-        const dim3 gridh(gx * gy), blkh(512);              // one row of workgroups: halo_block_map
-#define YH_LAUNCH_HALO(BN_, TL_)                                                                                     \
-        do {                                                                                                         \
-            const size_t sm = conv_halo_smem_bytes<BN_>();                                                           \
-            static YhDevOnce attr_set;                                                                                  \
-            if (attr_set.need()) {                                                                                         \
-                attr_set.set((const void*)conv_halo_kernel<BN_, 0, TL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
-                attr_set.set((const void*)conv_halo_kernel<BN_, 1, TL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
-                attr_set.set((const void*)conv_halo_kernel<BN_, 2, TL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
-                attr_set.set((const void*)conv_halo_kernel<BN_, 3, TL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
-                attr_set.done();                                                                                      \
-            }                                                                                                        \
-            if (epi == 3)      conv_halo_kernel<BN_, 3, TL_><<<gridh, blkh, sm, sth>>>(k, hgeo);                     \
-            else if (epi == 2) conv_halo_kernel<BN_, 2, TL_><<<gridh, blkh, sm, sth>>>(k, hgeo);                     \
-            else if (epi == 1) conv_halo_kernel<BN_, 1, TL_><<<gridh, blkh, sm, sth>>>(k, hgeo);                     \
-            else               conv_halo_kernel<BN_, 0, TL_><<<gridh, blkh, sm, sth>>>(k, hgeo);                     \
-        } while (0)
-        if (tl) { if (bn == 64) YH_LAUNCH_HALO(64, true); else YH_LAUNCH_HALO(128, true); }
-        else    { if (bn == 64) YH_LAUNCH_HALO(64, false); else YH_LAUNCH_HALO(128, false); }
-#undef YH_LAUNCH_HALO
-        YH_CHECK_LAUNCH("yh_conv_igemm(halo)");
-        return YH_OK;
-    }
-    if (v3) {
-        const int bkt3 = conv_v3_bkt(d);          // conv_v3_variant already checked the addressing (conv_buf_ok, re-based)
-        const bool tl3 = bkt3 == 64 && (k.Ctot % 64) != 0;
-        const int epi = d->bnr_part ? 3 : (generic ? 2 : (d->stats ? 1 : 0));
-        const int bmt = (v3 == 1 || v3 == 4) ? 256 : 128;
-        const int stg = v3 == 4 ? 2 : (v3 == 1 ? (bkt3 == 64 ? 3 : 4) : (v3 == 2 ? (bkt3 == 64 ? 2 : 4) : (bkt3 == 64 ? 3 : 4)));
-        if (name_out) {
-            snprintf(name_out, name_len, "conv_v3_kernel<%d, %d, %d, %d, %d, %d, %d%s>", bmt, bn, v3 == 1 ? 4 : 2, v3 == 4 ? 4 : 2, bkt3, stg, epi,
-                     tl3 ? ", true" : ", false");
-            return YH_OK;
-        }
-        hipStream_t st3 = (hipStream_t)stream;
-        {
-            // measured: no gain on YOLOv5x inference (707 / 712 -> 691 / 717 img/s), -2 % on the YOLOv5l train step: off (YH_HALO_MAP=2 enables it)
-            static const int rowmajor3 = [] { const char* e = getenv("YH_HALO_MAP"); return (e && atoi(e) == 2) ? 0 : 1; }();
-            k.xgx = k.xgy = 0;
-            if (!k.cls && grid.y > 1 && grid.z == 1 && !rowmajor3) { k.xgx = (int)grid.x; k.xgy = (int)grid.y; grid = dim3(grid.x * grid.y, 1, 1); }
-        }
-#define YH_LAUNCH_V3W(BMT_, BN_, WM_, WN_, BKT_, STG_, TL_)                                                               \
-        do {                                                                                                         \
-            const size_t sm = conv3_smem_bytes<BMT_, BN_, WM_, BKT_, STG_>();                                        \
-            const dim3 blk(WM_ * WN_ * 64);                                                                           \
-            static YhDevOnce attr_set;                                                                                  \
-            if (attr_set.need()) {                                                                                         \
-                attr_set.set((const void*)conv_v3_kernel<BMT_, BN_, WM_, WN_, BKT_, STG_, 0, TL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
-                attr_set.set((const void*)conv_v3_kernel<BMT_, BN_, WM_, WN_, BKT_, STG_, 1, TL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
-                attr_set.set((const void*)conv_v3_kernel<BMT_, BN_, WM_, WN_, BKT_, STG_, 2, TL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
-                attr_set.set((const void*)conv_v3_kernel<BMT_, BN_, WM_, WN_, BKT_, STG_, 3, TL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
-                attr_set.done();                                                                                      \
-            }                                                                                                        \
-            if (epi == 3)      conv_v3_kernel<BMT_, BN_, WM_, WN_, BKT_, STG_, 3, TL_><<<grid, blk, sm, st3>>>(k);     \
-            else if (epi == 2) conv_v3_kernel<BMT_, BN_, WM_, WN_, BKT_, STG_, 2, TL_><<<grid, blk, sm, st3>>>(k);     \
-            else if (epi == 1) conv_v3_kernel<BMT_, BN_, WM_, WN_, BKT_, STG_, 1, TL_><<<grid, blk, sm, st3>>>(k);     \
-            else               conv_v3_kernel<BMT_, BN_, WM_, WN_, BKT_, STG_, 0, TL_><<<grid, blk, sm, st3>>>(k);     \
-        } while (0)
-#define YH_LAUNCH_V3(BMT_, BN_, WM_, BKT_, STG_, TL_) YH_LAUNCH_V3W(BMT_, BN_, WM_, 2, BKT_, STG_, TL_)
-        if (v3 == 4) YH_LAUNCH_V3W(256, 256, 2, 4, 64, 2, false);
-        else if (v3 == 1) { if (tl3) YH_LAUNCH_V3(256, 128, 4, 64, 3, true); else if (bkt3 == 64) YH_LAUNCH_V3(256, 128, 4, 64, 3, false); else YH_LAUNCH_V3(256, 128, 4, 32, 4, false); }
-        else if (v3 == 2) { if (tl3) YH_LAUNCH_V3(128, 128, 2, 64, 2, true); else if (bkt3 == 64) YH_LAUNCH_V3(128, 128, 2, 64, 2, false); else YH_LAUNCH_V3(128, 128, 2, 32, 4, false); }
-        else { if (tl3) YH_LAUNCH_V3(128, 64, 2, 64, 3, true); else if (bkt3 == 64) YH_LAUNCH_V3(128, 64, 2, 64, 3, false); else YH_LAUNCH_V3(128, 64, 2, 32, 4, false); }
-#undef YH_LAUNCH_V3W
-#undef YH_LAUNCH_V3
-        YH_CHECK_LAUNCH("yh_conv_igemm(v3)");
-        return YH_OK;
-    }
-    if (name_out) {
-        const int wm = bn == 128 ? 2 : 4, wn = bn == 128 ? 2 : 1, minw = bn == 32 ? 4 : (bn == 64 ? 3 : 2);
-        if (k.v2) {
-            const bool e8 = bn == 128;
-            snprintf(name_out, name_len, "conv_v2_kernel<%d, %d, %d, %d, %d, %d>", bn, e8 ? 4 : wm, e8 ? 2 : wn, e8 ? 4 : minw,
-                     d->bnr_part ? 3 : (generic ? 2 : (d->stats ? 1 : 0)), bkt);
-        }
-        else snprintf(name_out, name_len, "conv_igemm_kernel<%d, %d, %d, %s, %d>", bn, wm, wn, k.fast ? "true" : "false", minw);
-        return YH_OK;
-    }
-    if (k.v2) {
-        hipStream_t st2 = (hipStream_t)stream;
-        const int epi = d->bnr_part ? 3 : (generic ? 2 : (d->stats ? 1 : 0));
-        if (k.cls && k.mtiles >= CLS_INNER_MIN_TILES) grid = dim3(cls_inner_blocks(gx_all), gy, 1);
-#define YH_LAUNCH_V2(BN_, WM_, WN_, MINW_, BKT_)                                                               \
-        do {                                                                                                   \
-            const size_t sm = conv_smem_bytes<BN_, WM_, WN_, BKT_>();                                          \
-            const dim3 blk(WM_ * WN_ * 64);                                                                    \
-            if (epi == 3)      conv_v2_kernel<BN_, WM_, WN_, MINW_, 3, BKT_><<<grid, blk, sm, st2>>>(k);       \
-            else if (epi == 2) conv_v2_kernel<BN_, WM_, WN_, MINW_, 2, BKT_><<<grid, blk, sm, st2>>>(k);       \
-            else if (epi == 1) conv_v2_kernel<BN_, WM_, WN_, MINW_, 1, BKT_><<<grid, blk, sm, st2>>>(k);       \
-            else               conv_v2_kernel<BN_, WM_, WN_, MINW_, 0, BKT_><<<grid, blk, sm, st2>>>(k);       \
-        } while (0)
-        if (bn == 128) {                     // 8 waves: 4 per SIMD with two resident blocks, wave tile 32 x 64
-            if (bkt == 64) YH_LAUNCH_V2(128, 4, 2, 4, 64);
-            else           YH_LAUNCH_V2(128, 4, 2, 4, 32);
-        } else if (bn == 64) {
-            YH_LAUNCH_V2(64, 4, 1, 3, 32);   // (8 waves of 32 x 32 measured equal: LDS reads per MFMA double)
-        } else {
-            YH_LAUNCH_V2(32, 4, 1, 4, 32);
-        }
-#undef YH_LAUNCH_V2
-        YH_CHECK_LAUNCH("yh_conv_igemm(v2)");
-        return YH_OK;
-    }
-    hipStream_t st = (hipStream_t)stream;
-#define YH_LAUNCH_CONV(BN_, WM_, WN_, MINW_)                                                                  \
-    do {                                                                                                      \
-        const size_t sm = conv_smem_bytes<BN_, WM_, WN_>();                                                   \
-        if (k.fast) conv_igemm_kernel<BN_, WM_, WN_, true, MINW_><<<grid, block, sm, st>>>(k);                \
-        else        conv_igemm_kernel<BN_, WM_, WN_, false, MINW_><<<grid, block, sm, st>>>(k);               \
-    } while (0)
-    if (bn == 32) YH_LAUNCH_CONV(32, 4, 1, 4);
-    else if (bn == 64) YH_LAUNCH_CONV(64, 4, 1, 3);
-    else YH_LAUNCH_CONV(128, 2, 2, 2);
-#undef YH_LAUNCH_CONV
-    YH_CHECK_LAUNCH("yh_conv_igemm");
-    return YH_OK;
+    if (pl.family == FAM_HALO160 || pl.family == FAM_HALO) YH_CHECK_ARG(pl.k.v2 && !pl.k.cls, "yh_conv_igemm: the halo kernel needs the buffer-load path");
+    if (name_out) { conv_plan_name(pl, name_out, name_len); return YH_OK; }
+    return conv_launch(pl, (hipStream_t)stream);
 }
 }  // namespace
 
 extern "C" int yh_conv_igemm(const yh_conv_desc* d, yh_stream stream) { return conv_run(d, stream, nullptr, 0); }
+
+/* name of the kernel instantiation yh_conv_igemm launches for this descriptor, as profilers print it */
+extern "C" int yh_conv_kernel_name(const yh_conv_desc* d, char* buf, int buflen)
+{
+    YH_CHECK_ARG(buf && buflen >= 64, "yh_conv_kernel_name: buffer too small");
+    return conv_run(d, nullptr, buf, buflen);
+}
+
+/* rows of the BatchNorm partial-sum slab (d->stats) the launch for this descriptor writes */
+extern "C" int yh_conv_stat_blocks(const yh_conv_desc* d)
+{
+    if (!conv_desc_plannable(d)) return 0;
+    yh_conv_desc d0;
+    int rows;
+    if (conv_sibling(d, &d0, SIB_STAT, &rows)) return rows;
+    ConvPlan pl;
+    return conv_plan(d, &pl) ? pl.stat_rows : 0;
+}
 
 /* rows of the partial-sum slab a data-gradient launch with the fused BatchNorm-backward reduction (bnr_*) writes:
  * [rows][2][N] floats (sum dz | sum dz*z), consumed by yh_bn_bwd_finalize(part, rows, ...).  0: this descriptor
@@ -2920,39 +2939,12 @@ extern "C" int yh_conv_igemm(const yh_conv_desc* d, yh_stream stream) { return c
 extern "C" int yh_conv_bnr_rows(const yh_conv_desc* d)
 {
     if (!conv_desc_plannable(d) || d->mode != YH_CONV_DGRAD || d->nseg != 1 || d->seg[0].C % 8 || d->seg[0].ups || d->N % 8) return 0;
-    if (d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->nsplit < d->N || d->stats) return 0;
-    if (conv_dbg_mask() & 16) return 0;
-    if (d->algo == 7 || d->algo == 8 || d->algo == 13) {
-        const int r7 = d->algo == 7 ? yh_dg2_rows(d) : (d->algo == 8 ? yh_p3_rows(d) : yh_pt_rows(d));
-        if (r7 > 0) return r7;
-        yh_conv_desc d0 = *d;
-        d0.algo = 0;
-        return yh_conv_bnr_rows(&d0);
-    }
-    const unsigned long M = (unsigned long)d->B * d->Ho * d->Wo;
-    if (M >= (1ul << 31) - BM) return 0;
-    const unsigned long npix = (unsigned long)d->B * d->Hi * d->Wi;
-    if (((npix - 1) * d->seg[0].ld + d->seg[0].C) * 2 >= (1ul << 31)) return 0;
-    if ((unsigned long)d->Npad * d->KH * d->KW * d->seg[0].C * 2 >= (1ul << 31)) return 0;
-    int gx, gy, bn;
-    conv_grid(d, &gx, &gy, &bn);
-    const bool cls = d->stride == 2 && d->Ho % 2 == 0 && d->Wo % 2 == 0 && d->KH >= 2 && d->KW >= 2;
-    if (!stem_eligible(d) && conv_halo_ok(d, nullptr)) return gx;
-    const int zslots = d->KH * d->KW;
-    if (conv_v3_variant(d)) return cls ? gx * zslots : gx;
-    if (cls) {
-        const long mt = ((long)(M / 4) + BM - 1) / BM;          // conv_v2_kernel (the only non-v3 kernel with this epilogue): one row per block
-        if (mt >= CLS_INNER_MIN_TILES) return cls_inner_blocks(gx < mt ? gx : (int)mt);
-        return cls_blocks_per_slot(gx, zslots, mt) * zslots;
-    }
-    return gx;
-}
-
-/* name of the kernel instantiation yh_conv_igemm launches for this descriptor, as profilers print it */
-extern "C" int yh_conv_kernel_name(const yh_conv_desc* d, char* buf, int buflen)
-{
-    YH_CHECK_ARG(buf && buflen >= 64, "yh_conv_kernel_name: buffer too small");
-    return conv_run(d, nullptr, buf, buflen);
+    if (conv_generic_na(d) || d->stats || (conv_dbg_mask() & 16)) return 0;
+    yh_conv_desc d0;
+    int rows;
+    if (conv_sibling(d, &d0, SIB_BNR, &rows)) return rows;
+    ConvPlan pl;
+    return conv_plan(d, &pl) ? pl.bnr_rows : 0;
 }
 
 /* diagnostics: a device buffer of grid x 8 x 8 uint64 that receives cycle sums of every workgroup's 2nd tile in conv_halo160_kernel (NULL: off) */
@@ -2966,12 +2958,14 @@ extern "C" int yh_debug_read_stamps(long long* host_out32)
 #endif
 
 // diagnostics: resident blocks per CU the runtime predicts for each instantiation (bn = 32/64/128)
+template <int BN> static hipError_t conv_generic_occupancy(int* nb)
+{
+    constexpr ConvTile T = conv_tile(BN);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(nb, conv_igemm_kernel<BN, T.wm, T.wn, true, T.minw>, 256, conv_smem_bytes<BN, T.wm, T.wn>());
+}
 extern "C" int yh_debug_conv_occupancy(int bn)
 {
     int nb = -1;
-    hipError_t e;
-    if (bn == 32) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_igemm_kernel<32, 4, 1, true, 4>, 256, conv_smem_bytes<32, 4, 1>());
-    else if (bn == 64) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_igemm_kernel<64, 4, 1, true, 3>, 256, conv_smem_bytes<64, 4, 1>());
-    else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_igemm_kernel<128, 2, 2, true, 2>, 256, conv_smem_bytes<128, 2, 2>());
+    const hipError_t e = bn == 32 ? conv_generic_occupancy<32>(&nb) : (bn == 64 ? conv_generic_occupancy<64>(&nb) : conv_generic_occupancy<128>(&nb));
     return e == hipSuccess ? nb : -(int)e;
 }
