@@ -125,6 +125,24 @@ def bn_fold(gamma, beta, rm, rv, eps, Cn, scale, shift):
     check(lib().yh_bn_fold(_p(gamma), _p(beta), _p(rm), _p(rv), eps, Cn, _p(scale), _p(shift), _st()), "yh_bn_fold")
 
 
+def bn_frozen(gamma, beta, rm, rv, eps, Cn, ws):
+    """evaluation-mode BatchNorm constants from the running statistics: ws = scale | shift | mean | invstd"""
+    check(lib().yh_bn_frozen(_p(gamma), _p(beta), _p(rm), _p(rv), eps, Cn, _p(ws), _st()), "yh_bn_frozen")
+
+
+def bn_fold_batch(items):
+    """items: dicts with gamma, beta, rm, rv, scale, shift (tensors) and eps; returns the device table (keep it alive until the launch ran)"""
+    from ._lib import BnFoldItem
+    arr = (BnFoldItem * len(items))()
+    for a, q in zip(arr, items):
+        for k in ("gamma", "beta", "rm", "rv", "scale", "shift"):
+            setattr(a, k, q[k].data_ptr())
+        a.eps, a.C = q["eps"], q["gamma"].numel()
+    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(items[0]["gamma"].device)
+    check(lib().yh_bn_fold_batch(_p(table), len(items), _st()), "yh_bn_fold_batch")
+    return table
+
+
 def bn_silu_apply(y: Slice, ws, M, out: Slice, res: Slice = None):
     check(lib().yh_bn_silu_apply(y.ptr(), y.ld, _p(ws), y.C, M, out.ptr(), out.ld,
                                  res.ptr() if res else None, res.ld if res else 0, _st()), "yh_bn_silu_apply")
@@ -216,6 +234,11 @@ def fill_zero(t):
     nbytes = t.numel() * t.element_size()
     assert nbytes % 4 == 0
     check(lib().yh_fill_u32(_p(t), 0, nbytes // 4, _st()), "yh_fill_u32")
+
+
+def fill_u32(t, value, n_words, word_off=0):
+    """n_words 32-bit words of t, from word `word_off` on, set to `value`"""
+    check(lib().yh_fill_u32(C.c_void_p(t.data_ptr() + 4 * word_off), value, n_words, _st()), "yh_fill_u32")
 
 
 def pack_bf16(src, idx, dst):
