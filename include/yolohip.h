@@ -164,7 +164,15 @@ typedef struct yh_wgrad_desc {
     /* optional workspace of >= yh_conv_wgrad_ws_bytes() bytes (16-byte aligned, caller-owned, may be shared by launches on ONE
      * stream): the split-M partial tiles are written there with plain stores and summed into dw by a second kernel in split
      * order — bit-reproducible, and faster than the fp32 atomics of the default form (NULL), which are bound by the atomic rate
-     * of L2.  dw is read-modify-written by that kernel: launches that share dw columns must be stream-ordered. */
+     * of L2.  dw is read-modify-written by that kernel: launches that share dw columns must be stream-ordered.
+     * The form of the launch decides the layout and yh_conv_wgrad_ws_bytes() answers for it: with tile_k 129 where
+     * yh_conv_wgrad_wave_tiles() > 0, conv_wgs_kernel keeps its stream-K schedule and writes one 128 x 128 fp32 tile (64 KB) per
+     * (workgroup, tile) pair into slot v + t (v: virtual workgroup, t: tile), G + T - 1 slots for G = min(splits, T * M / 32)
+     * workgroups and T tiles; wgs_reduce_kernel then adds the slots of every tile to dw in ascending v (yh_conv_wgrad_wave_name()
+     * reports conv_wgs_kernel<PW, true>).  As above: launches that share one workspace must run on ONE stream, and dw is
+     * read-modify-written.  The patch form (tile_k 40) and the fused stem backward (bn_z) have no workspace form of their own:
+     * with a workspace such launches go through conv_wgrad_kernel's.  A workspace that is too small or unaligned: YH_EINVAL,
+     * nothing is launched. */
     float*   partial;
     uint64_t partial_bytes;
     /* Fused BatchNorm+SiLU backward for a layer WITHOUT a data gradient (the stem: its input is the image): with bn_z != NULL

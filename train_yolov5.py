@@ -279,7 +279,12 @@ def main(argv=None, training_cls=None, default_cfg=None):
     ap.add_argument("--data", choices=["tensor", "dataset", "shapes"], help="tensor: random-noise batches; dataset: synthetic images "
                     "through DataLoader + fixed_imgsize_collate_fn + DataPrefetcher (the reference's data path); shapes: a learnable "
                     "task (coloured rectangles, colour = class) that shows mAP rising")
+    ap.add_argument("--deterministic", action="store_true", help="bit-reproducible weight gradients (yoloseries_amd.set_deterministic): "
+                    "two runs on the same seed and data write the same checkpoint")
     args = ap.parse_args(argv)
+    if args.deterministic:                                               # before any model / program is built
+        import yoloseries_amd
+        yoloseries_amd.set_deterministic(True)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         torch.cuda.set_device(get_local_rank())
         torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", get_local_rank()))

@@ -132,6 +132,7 @@ int yh_wgp_run(const yh_wgrad_desc* d, yh_stream stream);
 int yh_wgs_ok(const yh_wgrad_desc* d);
 int yh_wgs_tiles(const yh_wgrad_desc* d);
 const char* yh_wgs_name(const yh_wgrad_desc* d);
+size_t yh_wgs_ws_bytes(const yh_wgrad_desc* d);
 int yh_wgs_run(const yh_wgrad_desc* d, yh_stream stream);
 
 static inline bool yh_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }

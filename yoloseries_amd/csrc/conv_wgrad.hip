@@ -462,10 +462,13 @@ static void wg_split_plan(const yh_wgrad_desc* d, long M, int* tk_out, int* rps_
     *tk_out = TK; *rps_out = rps; *splits_out = splits;
 }
 
-/* bytes of workspace (yh_wgrad_desc.partial) a launch with these dims / splits needs for the plain-store partial tiles */
+/* bytes of workspace (yh_wgrad_desc.partial) a launch with these dims / splits / tile_k needs for the plain-store partial tiles:
+ * the form the launch will take decides — tile_k 129 where conv_wgs_kernel is eligible: its G + T - 1 slots of 64 KB; every other
+ * launch (the patch form and the fused stem backward have no workspace form: they go through conv_wgrad_kernel's): split-M tiles */
 extern "C" size_t yh_conv_wgrad_ws_bytes(const yh_wgrad_desc* d)
 {
     if (!d || d->B <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->N <= 0 || d->seg.C <= 0 || d->KH <= 0 || d->KW <= 0) return 0;
+    if (d->tile_k == 129 && yh_wgs_ok(d)) return yh_wgs_ws_bytes(d);
     const long M = (long)d->B * d->Ho * d->Wo;
     int tk, rps, splits;
     wg_split_plan(d, M, &tk, &rps, &splits);

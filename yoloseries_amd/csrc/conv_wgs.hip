@@ -19,6 +19,21 @@
 //   * the four partial tiles of a workgroup are combined through LDS (reduce-scatter in two exchange rounds of plain 16-byte
 //     stores / loads, every wave ends with one quarter) and leave as ONE set of fp32 atomics per workgroup and tile: half the
 //     adds of two independent blocks per CU.
+// Workspace form (yh_wgrad_desc.partial set; conv_wgs_kernel<PW, true> + wgs_reduce_kernel): bit-reproducible.  Everything up to and
+// including the LDS combine is the code above (that combine is fixed-order); the wave's quarter then leaves by plain 16-byte
+// stores into a SLOT of the workspace instead of atomics, and a second kernel on the same stream adds the slots of a tile to dw
+// in a fixed order.
+//   * slot = one whole 128 x 128 fp32 tile (64 KB), always written in full (dead rows / columns hold zeros), laid out as the
+//     registers lie: float4 index (wave * 16 + (xx * 2 + yy) * 4 + r4) * 64 + lane holds registers 4 r4 .. 4 r4 + 3 of the wave's
+//     kept accumulator [xx][yy], i.e. rows 64 hx + 32 xx + 8 r4 + 4 (lane >> 5) + 0..3 of column 64 hy + 32 yy + (lane & 31);
+//     every store instruction writes 1 KiB contiguous;
+//   * slot index = v + t for VIRTUAL workgroup v (after the phase map) and tile t.  Workgroup v owns the units [v U / G, (v+1) U / G)
+//     of the tile-major order, so the (v, t) pairs that intersect form a staircase (v < v' implies t <= t'): v + t is unique, and
+//     G + T - 1 slots suffice (yh_conv_wgrad_ws_bytes);
+//   * wgs_reduce_kernel: tile t is covered by the workgroups va .. vb that own its first and last unit (the owner of unit u is
+//     ((u + 1) G - 1) / U, the inverse of the kernel's range formula); their slots are added in ascending v (split over the
+//     block's wave-rows as wgrad_reduce_kernel does, met in LDS in a fixed order), then dw is read-modify-written with the N and
+//     tap bounds of the atomic epilogue.  It reads only slots the main kernel has written.
 // Replaces autograd's conv weight gradient (train_yolov5.py:337 -> utils/layer_tools.py:82-94).
 #include "common.h"
 #include <stdlib.h>
@@ -33,6 +48,7 @@ constexpr int WGS_STAGE = 8192;                      // bytes per stage: A [16 p
 constexpr int WGS_WAVE_LDS = WGS_STG * WGS_STAGE;    // 32 KB per wave
 constexpr int WGS_LDS = 4 * WGS_WAVE_LDS;            // 128 KB per workgroup
 constexpr unsigned WGS_OOB = 0x80000000u;
+constexpr size_t WGS_SLOT = 128 * 128 * sizeof(float);   // workspace form: bytes of a slot
 
 struct WgsK {
     yh_wgrad_desc d;
@@ -45,6 +61,7 @@ struct WgsK {
     long U;            // T * nk work units
     unsigned gybytes, xbytes, dwbytes;
     int pw;            // 1x1 / stride 1 / pad 0 layer on a plain segment (the kernel's PW form)
+    float* ws;         // workspace form: G + T - 1 slots of one 128 x 128 fp32 tile
 };
 
 __device__ __forceinline__ v4s wgs_tr(const unsigned char* p) {
@@ -71,7 +88,8 @@ __device__ __forceinline__ void wgs_dma(unsigned lds, unsigned voff, const __amd
 }
 
 // PW: 1x1 / stride 1 / pad 0 layer on a plain segment (the im2col row IS the pixel's row: scalar walk)
-template <bool PW>
+// WS: the wave's quarter leaves by plain stores into workspace slot v + t (file header) instead of atomics into dw
+template <bool PW, bool WS>
 __device__ __forceinline__ void wgs_body(const WgsK& p, const int bidx, unsigned char* const smem)
 {
     const yh_wgrad_desc& d = p.d;
@@ -313,7 +331,20 @@ __device__ __forceinline__ void wgs_body(const WgsK& p, const int bidx, unsigned
         // holds row (r & 3) + 8 (r >> 2) + 4 (lane >> 5): one wave instruction adds two 128-byte row segments.  Buffer atomics:
         // the row walk is a SCALAR offset (no address arithmetic per add, one offset register), rows past N carry an
         // out-of-range offset instead of an exec mask.
-        {
+        if constexpr (WS) {
+            // the slot is written whole: rows past N and columns past the last tap were fed zeros (out-of-range operand offsets).
+            // Plain global stores of 16 bytes (no scalar offset: the compiler keeps their wait state in front of a write to the data)
+            float4* const slot = reinterpret_cast<float4*>(p.ws) + ((size_t)(v + t) * 4096 + wave * 1024 + lane);
+#pragma unroll
+            for (int xy = 0; xy < 4; ++xy) {
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const f32x16_t& a = acc[xy >> 1][xy & 1];
+                    slot[(xy * 4 + r4) * 64] = make_float4(a[4 * r4], a[4 * r4 + 1], a[4 * r4 + 2], a[4 * r4 + 3]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
             const int nl = n0 + 64 * hx + 4 * (lane >> 5);
             // the two 32-column groups of this wave's quarter: tap and channel of a group are wave-uniform (32 | C)
             const int col0 = ctile * 128 + 64 * hy, col1 = col0 + 32;
@@ -348,7 +379,68 @@ template <bool PW>
 __global__ __launch_bounds__(256, 1) void conv_wgs_kernel(const WgsK p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    wgs_body<PW>(p, blockIdx.x, smem);
+    wgs_body<PW, false>(p, blockIdx.x, smem);
+}
+// the workspace form: an overload with a second template argument, so that the atomic form keeps its name (conv_wgs_kernel<PW>)
+template <bool PW, bool WS>
+__global__ __launch_bounds__(256, 1) void conv_wgs_kernel(const WgsK p)
+{
+    static_assert(WS, "the atomic form is conv_wgs_kernel<PW>");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    wgs_body<PW, true>(p, blockIdx.x, smem);
+}
+
+struct WgsR {
+    const float* ws; float* dw;
+    int N, Ktot, Ctot, coffk, segC, ntap, nk, nct, G;
+    long U;
+};
+
+// dw[n][tap * Ctot + coff_k + c] += sum over the workgroups v = va .. vb of tile t (ascending) of slot v + t.  A block sums ONE
+// 1 KiB chunk (64 float4) of the tile; its SG wave-rows take v = va + sg, va + sg + SG, ... and meet in LDS in a fixed order.
+__global__ __launch_bounds__(1024) void wgs_reduce_kernel(const WgsR p)
+{
+    __shared__ float4 sred[16][64];
+    const int SG = blockDim.y, sg = threadIdx.y, lane = threadIdx.x;
+    const int t = blockIdx.y, q = blockIdx.x;                 // q = wave * 16 + (xx * 2 + yy) * 4 + r4 of the slot layout
+    const int ntile = t / p.nct, ctile = t - ntile * p.nct;
+    const int w = q >> 4, hx = w & 1, hy = w >> 1, xx = (q >> 3) & 1, yy = (q >> 2) & 1, r4 = q & 3;
+    const int nb = ntile * 128 + 64 * hx + 32 * xx + 8 * r4;   // the chunk's rows: nb + 4 (lane >> 5) + 0..3
+    const int col = ctile * 128 + 64 * hy + 32 * yy + (lane & 31);
+    const int tap = (col - (lane & 31)) / p.segC;              // 32 | C: the chunk's 32 columns share a tap
+    if (tap >= p.ntap || nb >= p.N) return;                    // dead chunk (uniform for the block)
+    const long ua = (long)t * p.nk, ub = ua + p.nk - 1;
+    const int va = (int)(((ua + 1) * p.G - 1) / p.U), vb = (int)(((ub + 1) * p.G - 1) / p.U);
+    const float4* src = reinterpret_cast<const float4*>(p.ws) + ((size_t)t * 4096 + q * 64 + lane);
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    int s = va + sg;
+    for (; s + 3 * SG <= vb; s += 4 * SG) {
+        const float4 v0 = src[(size_t)s * 4096];
+        const float4 v1 = src[(size_t)(s + SG) * 4096];
+        const float4 v2 = src[(size_t)(s + 2 * SG) * 4096];
+        const float4 v3 = src[(size_t)(s + 3 * SG) * 4096];
+        a.x += v0.x; a.y += v0.y; a.z += v0.z; a.w += v0.w;
+        a.x += v1.x; a.y += v1.y; a.z += v1.z; a.w += v1.w;
+        a.x += v2.x; a.y += v2.y; a.z += v2.z; a.w += v2.w;
+        a.x += v3.x; a.y += v3.y; a.z += v3.z; a.w += v3.w;
+    }
+    for (; s <= vb; s += SG) {
+        const float4 v0 = src[(size_t)s * 4096];
+        a.x += v0.x; a.y += v0.y; a.z += v0.z; a.w += v0.w;
+    }
+    sred[sg][lane] = a;
+    __syncthreads();
+    if (sg != 0) return;
+    for (int g = 1; g < SG; ++g) {
+        const float4 o = sred[g][lane];
+        a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+    }
+    const int n = nb + 4 * (lane >> 5);
+    float* dst = p.dw + ((size_t)n * p.Ktot + (size_t)tap * p.Ctot + p.coffk + (col - tap * p.segC));
+    const float r[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (n + j < p.N) dst[(size_t)j * p.Ktot] += r[j];
 }
 
 // eligibility of the layer and the launch plan shared by the queries and the launcher
@@ -369,7 +461,7 @@ bool wgs_plan(const yh_wgrad_desc* d, WgsPlan* pl)
     if (d->KH > 7 || d->KW > 7 || (d->stride != 1 && d->stride != 2) || d->pad < 0) return false;
     if (d->ldg % 8 != 0 || d->ldg < (d->N + 7) / 8 * 8) return false;
     if (!wgs_seg_ok(d, d->seg, d->coff_k, &pl->xb)) return false;
-    if (d->bn_z || d->partial) return false;
+    if (d->bn_z) return false;
     if ((d->Hi + 2 * d->pad - d->KH) / d->stride + 1 != d->Ho || (d->Wi + 2 * d->pad - d->KW) / d->stride + 1 != d->Wo) return false;
     const long M = (long)d->B * d->Ho * d->Wo;
     if (M % 32 != 0 || M >= (1L << 31) - 256 || d->Ho * d->Wo < 16) return false;
@@ -404,7 +496,14 @@ const char* yh_wgs_name(const yh_wgrad_desc* d)
 {
     WgsPlan pl;
     if (!wgs_plan(d, &pl)) return "";
+    if (d->partial) return pl.pw ? "conv_wgs_kernel<true, true>" : "conv_wgs_kernel<false, true>";
     return pl.pw ? "conv_wgs_kernel<true>" : "conv_wgs_kernel<false>";
+}
+/* workspace form: bytes of the G + T - 1 slots of one 128 x 128 fp32 tile (G after the clamp to the layer's units) */
+size_t yh_wgs_ws_bytes(const yh_wgrad_desc* d)
+{
+    WgsPlan pl;
+    return wgs_plan(d, &pl) ? (size_t)(pl.G + pl.T - 1) * WGS_SLOT : 0;
 }
 
 // kernel parameters of one layer on G workgroups (block map, descriptor ranges, diagnostics)
@@ -429,6 +528,7 @@ static void wgs_fill(const yh_wgrad_desc* d, const WgsPlan& pl, int G, WgsK* kp)
     k.xbytes = (unsigned)pl.xb;
     k.dwbytes = (unsigned)((unsigned long)d->N * d->KH * d->KW * d->Ctot * 4);
     k.pw = pl.pw ? 1 : 0;
+    k.ws = d->partial;
     // timing-only diagnostics (results wrong): YH_WGS_ABL bit 0: zero-record operand descriptors (every transfer returns zeros without
     // touching memory: the loop's issue-bound time), bit 1: zero-record dw descriptor (the atomics are dropped by the range check)
     static const int abl = [] { const char* e = getenv("YH_WGS_ABL"); return e ? atoi(e) : 0; }();
@@ -442,6 +542,8 @@ static void wgs_attrs()
     if (attr_set.need()) {
         attr_set.set((const void*)conv_wgs_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, WGS_LDS);
         attr_set.set((const void*)conv_wgs_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, WGS_LDS);
+        attr_set.set((const void*)conv_wgs_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, WGS_LDS);
+        attr_set.set((const void*)conv_wgs_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, WGS_LDS);
         attr_set.done(); 
     }
 }
@@ -456,6 +558,24 @@ int yh_wgs_run(const yh_wgrad_desc* d, yh_stream stream)
     wgs_fill(d, pl, pl.G, &k);
     wgs_attrs();
     hipStream_t st = (hipStream_t)stream;
+    if (d->partial) {
+        // main kernel -> slots, then the fixed-order sum into dw on the same stream (the caller has checked the workspace's size)
+        YH_CHECK_ARG(yh_aligned16(d->partial) && d->partial_bytes >= (size_t)(pl.G + pl.T - 1) * WGS_SLOT && pl.T <= 65535,
+                     "yh_conv_wgrad(tile_k 129): workspace too small / unaligned");
+        if (pl.pw) conv_wgs_kernel<true, true><<<dim3(pl.grid), dim3(256), WGS_LDS, st>>>(k);
+        else       conv_wgs_kernel<false, true><<<dim3(pl.grid), dim3(256), WGS_LDS, st>>>(k);
+        YH_CHECK_LAUNCH("yh_conv_wgrad(tile_k 129, workspace)");
+        WgsR r;
+        r.ws = d->partial; r.dw = d->dw;
+        r.N = d->N; r.Ktot = k.Ktot; r.Ctot = d->Ctot; r.coffk = d->coff_k; r.segC = d->seg.C; r.ntap = d->KH * d->KW;
+        r.nk = pl.nk; r.nct = pl.nct; r.G = pl.G; r.U = k.U;
+        const int cnt = (pl.G + pl.T - 1) / pl.T + 1;      // at most this many workgroups touch a tile
+        int sg = 1;
+        while (sg < 16 && sg * 4 < cnt) sg *= 2;
+        wgs_reduce_kernel<<<dim3(64, pl.T), dim3(64, sg), 0, st>>>(r);
+        YH_CHECK_LAUNCH("yh_conv_wgrad(tile_k 129, reduce)");
+        return YH_OK;
+    }
     if (pl.pw) conv_wgs_kernel<true><<<dim3(pl.grid), dim3(256), WGS_LDS, st>>>(k);
     else       conv_wgs_kernel<false><<<dim3(pl.grid), dim3(256), WGS_LDS, st>>>(k);
     YH_CHECK_LAUNCH("yh_conv_wgrad(tile_k 129)");

@@ -84,8 +84,12 @@ class BackwardMixin:
         self.ups_scratch = {}
         self.wgrad_tuned = {}
         # workspace of the weight gradients' split-M partial tiles (plain stores + a deterministic reduce instead of fp32
-        # atomics; YH_WGRAD_PARTIAL=0: atomics).  One buffer serves every launch: they all run on one stream, in order.
+        # atomics; set_deterministic(False) / YH_WGRAD_PARTIAL=0: atomics).  One buffer serves every launch: they all run on one
+        # stream, in order.  While the program is built the launches are timed against a buffer of the cap's size; the program
+        # keeps one of the size its largest launch needs (below).
+        self.bwd_deterministic = _flags.WG_WS_BYTES > 0
         self.wg_ws = torch.empty(_flags.WG_WS_BYTES // 4, dtype=torch.float32, device=self.dev) if _flags.WG_WS_BYTES > 0 else None
+        wg_descs = []
 
         writes_seen = {}
 
@@ -284,6 +288,7 @@ class BackwardMixin:
                 nbytes_x = 2.0 * B * (op.Hi >> sg.ups) * (op.Wi >> sg.ups) * sg.C
                 wd.splits = self._tune_wgrad_splits(wd, M, ntile, op)
                 self._keep.append(wd)
+                wg_descs.append(wd)
                 if on_main:
                     self._wgrad_on_main.add(id(wd))
                 launches.append((op, wd, (self._wgrad_name(L, wd), 2.0 * M * op.N * kcols,
@@ -348,6 +353,14 @@ class BackwardMixin:
                         d.bnr_part = slab.data_ptr()
                         self.bnr_fused[(po.name, ppi)] = (slab, rows)
                     cmds.append(('dgrad', op, d, (self._kernel_name(d), 2.0 * M * op.N * op.k * op.k * sg.C, self._conv_bytes(d))))
+        if self.wg_ws is not None:       # the shared workspace: what the largest launch of the program needs
+            need = max([int(L.yh_conv_wgrad_ws_bytes(C.byref(wd))) for wd in wg_descs] + [16])
+            if need > self.wg_ws.numel() * 4:
+                raise YoloHipError(f"weight-gradient workspace: a launch needs {need} bytes, the cap is {self.wg_ws.numel() * 4}")
+            self.wg_ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.dev)
+            for wd in wg_descs:
+                wd.partial, wd.partial_bytes = self.wg_ws.data_ptr(), self.wg_ws.numel() * 4
+        _flags.note_backward_built(self)
         self.cmd_bwd = cmds
         self.cmd_bwd_frozen = None
         self.bwd_buckets = plan_grad_buckets(marks, pk.gsize, int(os.environ.get("YH_DP_BUCKETS", "4")))

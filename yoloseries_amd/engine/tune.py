@@ -103,7 +103,7 @@ _WGRAD_TK64 = {
 # version prefixes of the tuning-table keys: bumped when the candidates or the meaning of a tuned value change, so that stale
 # entries of a shipped / cached table are not applied.  Stride-2 data gradients carry their own version (conv_dg2_kernel, algo 7,
 # joined their candidates in round 3), and so do weight gradients that leave through the partial-tile workspace.
-KEY_CONV, KEY_CONV_S2D, KEY_CONV_P3, KEY_CONV_EVAL, KEY_WGRAD, KEY_WGRAD_WS = "conv6", "conv7", "conv8", "conv9", "wgrad10", "wgrad8"
+KEY_CONV, KEY_CONV_S2D, KEY_CONV_P3, KEY_CONV_EVAL, KEY_WGRAD, KEY_WGRAD_WS = "conv6", "conv7", "conv8", "conv9", "wgrad10", "wgrad11"   # wgrad11: conv_wgs_kernel's workspace form joined the workspace candidates (wgrad8 entries never saw it)
 KEY_CONV_C80 = "conv10"        # inference 3x3 layers with 80 -> 160 channels: conv_c80_kernel (algo 12) joined their candidates in round 4
 KEY_CONV_PT = "conv11"         # 1x1 layers conv_pt_kernel (algo 13) takes: training with 128 / 256 / 512 input channels, inference with 320 (round 5)
 KEY_CONV_H160 = "conv14"       # inference 3x3 / stride-1 layers with N a multiple of 160: re-timed against the FINAL conv_halo160_kernel of round 5 (16 x 16 tiles, pipelined sub-steps): it now takes every one of them, also the 640-channel layers the conv12 entries had left on conv_halo_kernel
@@ -223,8 +223,10 @@ class TunerMixin:
                                                           wd.Hi, wd.Wi, wd.KH, wd.stride, wd.pad))
         cache = _tune_cache()
         if key in cache:
-            sp, wd.tile_k = (int(v) for v in cache[key])
-            return sp
+            sp, tk = (int(v) for v in cache[key])
+            wd.splits, wd.tile_k = sp, tk
+            if not wd.partial or self.L.yh_conv_wgrad_ws_bytes(C.byref(wd)) <= wd.partial_bytes:
+                return sp                  # (a choice timed with a larger workspace than this program's is timed again)
         gy_saved = wd.gy
         if not wd.gy:                      # head gradient arrives at run time: time against the scratch buffer
             if self.gy_scratch.numel() < M * wd.ldg:
@@ -241,9 +243,10 @@ class TunerMixin:
         wd.tile_k = 40
         if not wd.partial and self.L.yh_conv_wgrad_patch_ok(C.byref(wd)):
             tks = tks + (40,)               # patch form (conv_wgp_kernel): the input patch of a pixel region staged once in LDS
-        wtiles = 0 if (wd.partial or wd.bn_z or os.environ.get("YH_WGRAD_WAVE", "1") == "0") else self.L.yh_conv_wgrad_wave_tiles(C.byref(wd))
+        wtiles = 0 if (wd.bn_z or os.environ.get("YH_WGRAD_WAVE", "1") == "0") else self.L.yh_conv_wgrad_wave_tiles(C.byref(wd))
         if wtiles > 0:
-            tks = tks + (129,)              # wave-private 128 x 128 tiles + stream-K (conv_wgs_kernel): `splits` = workgroups, one per CU
+            tks = tks + (129,)              # wave-private 128 x 128 tiles + stream-K (conv_wgs_kernel): `splits` = workgroups, one per CU;
+                                            # with a workspace its slot form (same workgroup counts: G + tiles - 1 slots of 64 KB)
         for tk in tks:
             wd.tile_k = tk
             if tk == 129:                   # an exact tiles x splits grid where it fills the chip, else 256 workgroups dealt (tile, 32 pixels) units
