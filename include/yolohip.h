@@ -189,8 +189,18 @@ int yh_conv_wgrad(const yh_wgrad_desc* d, yh_stream stream);
 size_t yh_conv_wgrad_ws_bytes(const yh_wgrad_desc* d);
 int yh_conv_wgrad_patch_ok(const yh_wgrad_desc* d);
 int yh_conv_wgrad_patch_name(const yh_wgrad_desc* d, char* buf, int buflen);   /* instantiation of the patch form, profiler spelling */
-const char* yh_conv_wgrad_kernel_name(int N, int Kseg);   /* instantiation used for a layer (tile_k 0), profiler spelling */
-const char* yh_conv_wgrad_kernel_name2(int N, int Kseg, int tile_k);
+/* What yh_conv_wgrad(d) will launch, decided by the same plan.  Needs no device and dereferences no operand.  Returns the rc
+ * yh_conv_wgrad would return from its own checks (the wave form's launcher adds operand checks of its own); `out` is filled from
+ * the dims alone — as yh_conv_wgrad_ws_bytes answers — whenever B, Ho, Wo, N, C, KH, KW are positive, also beside a non-zero rc. */
+typedef struct yh_wgrad_info {
+    int32_t  form;                    /* 0 im2col (conv_wgrad_kernel), 1 patch (conv_wgp_kernel), 2 wave (conv_wgs_kernel) */
+    int32_t  tiles;                   /* tiles of that form: yh_conv_wgrad_tiles2() / yh_conv_wgrad_wave_tiles() */
+    int32_t  splits;                  /* im2col: splits that hold pixels after rounding to whole k-steps; else `splits` as given */
+    int32_t  tile_k;                  /* the request in tile_k where it changed the launch, 0 where it was ignored */
+    uint64_t ws_bytes;                /* yh_conv_wgrad_ws_bytes(d) */
+    char     name[96];                /* the kernel instantiation, profiler spelling */
+} yh_wgrad_info;
+int yh_conv_wgrad_info(const yh_wgrad_desc* d, yh_wgrad_info* out);
 /* number of (out-channel x im2col-column) tiles the kernel uses for a layer; callers size `splits` so that
  * tiles*splits is about one resident wave of blocks */
 int yh_conv_wgrad_tiles(int N, int Kseg);

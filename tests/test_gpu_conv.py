@@ -166,6 +166,95 @@ def test_conv_wgrad(dev, B, H, W, Cin, Cout, k, s, p, splits, tile_k):
     assert lib().yh_conv_wgrad(C.byref(d), None) != 0      # a workspace that is too small is refused
 
 
+# every conv_wgrad_kernel instantiation with the smallest layer that reaches it: (k, Cin, Cout, tile_k, fused BatchNorm backward,
+# template arguments <WN, WC, TNW, TCW, TK, MINW, PF2>)
+WGRAD_ROWS = [(k, ci, co, tk, fbn, args)
+              for k, ci, co, fusable, variants in [
+                  (3, 16, 32, True, ((0, "1, 5, 1, 1, 32, 3, true"), (64, "1, 5, 1, 1, 64, 3, true"))),           # stem row (144 columns)
+                  (1, 192, 32, True, ((0, "1, 4, 1, 2, 32, 3, true"), (64, "1, 4, 1, 2, 64, 2, true"))),
+                  (3, 32, 32, False, ((0, "1, 4, 1, 3, 32, 3, false"), (64, "1, 4, 1, 3, 64, 2, false"))),
+                  (1, 64, 64, False, ((0, "1, 4, 2, 1, 32, 4, false"), (64, "1, 4, 2, 1, 64, 2, false"))),
+                  (3, 16, 64, True, ((0, "1, 4, 2, 2, 32, 3, false"), (64, "1, 4, 2, 2, 64, 2, false"))),
+                  (3, 32, 64, False, ((0, "1, 4, 2, 3, 32, 2, false"),)),
+                  (3, 64, 64, False, ((0, "2, 2, 1, 2, 64, 3, true"),)),
+                  (3, 64, 128, False, ((0, "4, 2, 1, 2, 64, 4, true"), (32, "4, 2, 1, 2, 32, 2, true"), (35, "2, 2, 2, 2, 32, 2, false")))]
+              for tk, args in variants for fbn in ((False, True) if fusable else (False,))]
+_wgrad_row_layers = {}
+
+
+def _wgrad_row_layer(dev, k, Cin, Cout):
+    """operands of one layer of WGRAD_ROWS (maps of 12 x 20, batch 2: 480 pixels — ragged against 32- and 64-pixel k-steps) and its
+    fp32 autograd weight gradient; for the fused rows gy is gz as yh_bn_silu_bwd_apply forms it from (ga, z)"""
+    key = (str(dev), k, Cin, Cout)
+    if key in _wgrad_row_layers:
+        return _wgrad_row_layers[key]
+    from yoloseries_amd import hipk
+    B, H, W = 2, 12, 20
+    x = _nhwc(B, H, W, Cin, dev, 311)
+    ga = _nhwc(B, H, W, Cout, dev, 312)
+    z = _nhwc(B, H, W, Cout, dev, 313)
+    z[0, :2] = 0.0
+    ga[0, 0] = 0.0
+    g = torch.Generator().manual_seed(314 + Cout)
+    mean, invstd = torch.randn(Cout, generator=g) * 0.3, torch.rand(Cout, generator=g) + 0.5
+    gamma = (torch.rand(Cout, generator=g) + 0.5).to(dev)
+    scale = gamma.cpu() * invstd
+    ws = torch.cat([scale, torch.randn(Cout, generator=g) * 0.2 - mean * scale, mean, invstd]).to(dev)
+    coef = torch.cat([torch.randn(Cout, generator=g) * 0.05, torch.randn(Cout, generator=g) * 0.05]).to(dev)
+    gz = torch.zeros(B, H, W, Cout, dtype=torch.bfloat16, device=dev)
+    hipk.bn_silu_bwd_apply(hipk.full(ga), hipk.full(z), ws, gamma, coef, B * H * W, hipk.full(gz))
+    torch.cuda.synchronize()
+
+    def ref_of(gy):
+        w = torch.zeros(Cout, Cin, k, k, device=dev, requires_grad=True)
+        (r,) = torch.autograd.grad(F.conv2d(_nchw(x), w, padding=k // 2), w, _nchw(gy))
+        return r.permute(0, 2, 3, 1).reshape(Cout, -1)
+    _wgrad_row_layers[key] = dict(x=x, ga=ga, z=z, gz=gz, ws=ws, gamma=gamma, coef=coef, ref_plain=ref_of(ga), ref_fused=ref_of(gz))
+    return _wgrad_row_layers[key]
+
+
+@pytest.mark.parametrize("k,Cin,Cout,tile_k,fbn,args", WGRAD_ROWS)
+def test_conv_wgrad_every_instantiation(dev, k, Cin, Cout, tile_k, fbn, args):
+    """each row of conv_wgrad.hip's instantiation table on the smallest layer the plan sends to it: the plan names the row, the
+    result meets test_conv_wgrad's bar (fp32 autograd, 2e-3 relative + 2e-3 of the largest magnitude) through the atomic and the
+    workspace form, the workspace form is bit-identical from launch to launch, and a fused row (bn_z: operands built as in
+    test_conv_wgrad_fused_bn_backward) is bit-identical to the plain row on the gz of the apply pass"""
+    import ctypes as C
+    from yoloseries_amd import hipk
+    from yoloseries_amd._lib import WgradInfo, lib
+    B, H, W, splits = 2, 12, 20, 3
+    t = _wgrad_row_layer(dev, k, Cin, Cout)
+    ref = t["ref_fused"] if fbn else t["ref_plain"]
+    scale = ref.abs().max().item()
+
+    def run(gy, fused, workspace, fill=0.0):
+        dw = torch.full((Cout, k * k * Cin), fill, device=dev)
+        d = hipk.wgrad_desc(hipk.full(gy), Cout, hipk.full(t["x"]), 0, Cin, B, H, W, H, W, k, 1, k // 2, dw, splits)
+        d.tile_k = tile_k
+        if fused:
+            d.bn_z, d.bn_ldz = t["z"].data_ptr(), Cout
+            d.bn_ws, d.bn_gamma, d.bn_coef = t["ws"].data_ptr(), t["gamma"].data_ptr(), t["coef"].data_ptr()
+        wsb = None
+        if workspace:
+            need = lib().yh_conv_wgrad_ws_bytes(C.byref(d))
+            wsb = torch.full((need // 4 + 64,), float("nan"), device=dev)
+            d.partial, d.partial_bytes = wsb.data_ptr(), need
+        o = WgradInfo()
+        assert lib().yh_conv_wgrad_info(C.byref(d), C.byref(o)) == 0
+        assert o.name.decode() == f"conv_wgrad_kernel<{args}, {'true' if fused else 'false'}>" and o.splits == splits
+        hipk.wgrad_launch(d)
+        torch.cuda.synchronize()
+        if workspace:
+            assert torch.isnan(wsb[need // 4:]).all()      # nothing written past the advertised size
+        return dw
+    _close(run(t["ga"], fbn, False), ref, 2e-3, 2e-3 * scale)
+    outs = [run(t["ga"], fbn, True, 0.25) for _ in range(2)]        # the reduce adds onto what dw holds
+    assert torch.equal(outs[0], outs[1])
+    _close(outs[0] - 0.25, ref, 2e-3, 2e-3 * scale)
+    if fbn:
+        assert torch.equal(outs[0], run(t["gz"], False, True, 0.25))
+
+
 WGP_CASES = [
     # B, H, W, Cin, Cout, stride, coff_k, Ctot
     (2, 40, 48, 16, 32, 1, 0, 16),       # stem class (space-to-depth image, 16 channels: two taps per 32-column tile, half a tile past tap 8)

@@ -32,7 +32,8 @@ def test_ctypes_struct_sizes_match_header_layout(tmp_path):
     import ctypes as C
     import subprocess
     from yoloseries_amd import _lib
-    pairs = [("yh_seg", _lib.Seg), ("yh_conv_desc", _lib.ConvDesc), ("yh_wgrad_desc", _lib.WgradDesc), ("yh_v5loss_desc", _lib.V5LossDesc),
+    pairs = [("yh_seg", _lib.Seg), ("yh_conv_desc", _lib.ConvDesc), ("yh_wgrad_desc", _lib.WgradDesc), ("yh_wgrad_info", _lib.WgradInfo),
+             ("yh_v5loss_desc", _lib.V5LossDesc),
              ("yh_yolox_desc", _lib.YoloxDesc), ("yh_decode_desc", _lib.DecodeDesc), ("yh_bn_fold_item", _lib.BnFoldItem),
              ("yh_bn_part", _lib.BnPart), ("yh_cmd", _lib.Cmd)]
     hdr = open(os.path.join(ROOT, "include", "yolohip.h")).read()
@@ -371,6 +372,176 @@ def test_conv_plan_table_is_stable():
     fams = {n.split("<")[0] for n in want["names"]}
     assert {"conv_stem_kernel", "conv_halo160_kernel", "conv_halo_kernel", "conv_v3_kernel", "conv_v2_kernel", "conv_igemm_kernel",
             "conv_dg2_kernel", "conv_p3_kernel", "conv_pt_kernel"} <= fams, fams
+
+
+def _wgrad_plan_table():
+    import importlib.util
+    import sys
+    tools = os.path.join(ROOT, "tools")
+    if tools not in sys.path:
+        sys.path.insert(0, tools)          # (the module imports conv_plan_table.digest)
+    spec = importlib.util.spec_from_file_location("wgrad_plan_table", os.path.join(tools, "wgrad_plan_table.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_wgrad_plan_table_is_stable():
+    """what yh_conv_wgrad decides — form, kernel instantiation, tiles, effective splits, honoured tile_k, workspace bytes — for every
+    shipped weight-gradient entry of the tuning table and 2 000 seeded random descriptors, through yh_conv_wgrad_info alone, against
+    the record tests/golden/wgrad_plan_digest.json (`tools/wgrad_plan_table.py --digest`, taken from the library as it was before the
+    decisions were consolidated into wg_plan, its columns composed from the queries of that time).  No device needed.  A deliberate
+    change of a plan regenerates the record; `tools/wgrad_plan_table.py --reduced` prints the lines of a chunk that differs"""
+    import json
+    from yoloseries_amd._lib import lib
+    mod = _wgrad_plan_table()
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "wgrad_plan_digest.json")))
+    got = mod.digest(mod.reduced(lib()), want["chunk"])
+    assert want["lines"] >= 2100 and got["lines"] == want["lines"]
+    assert got["names"] == want["names"], (sorted(set(got["names"]) - set(want["names"])), sorted(set(want["names"]) - set(got["names"])))
+    bad = [i for i, (g, w) in enumerate(zip(got["sha256"], want["sha256"])) if g != w]
+    assert not bad and len(got["sha256"]) == len(want["sha256"]), f"plans differ from the record in chunks {bad} (of {want['chunk']} lines each)"
+    assert {"conv_wgrad_kernel", "conv_wgp_kernel", "conv_wgpf_kernel", "conv_wgs_kernel"} <= {n.split("<")[0] for n in want["names"]}
+
+
+# the conv_wgrad_kernel instantiations of the library: <WN, WC, TNW, TCW, TK, MINW, PF2> and whether the row also exists fused
+WGRAD_ROWS = [("1, 5, 1, 1, 32, 3, true", True), ("1, 5, 1, 1, 64, 3, true", True), ("1, 4, 1, 2, 32, 3, true", True), ("1, 4, 1, 2, 64, 2, true", True),
+              ("1, 4, 1, 3, 32, 3, false", False), ("1, 4, 1, 3, 64, 2, false", False), ("1, 4, 2, 1, 32, 4, false", False),
+              ("1, 4, 2, 1, 64, 2, false", False), ("1, 4, 2, 2, 32, 3, false", True), ("1, 4, 2, 2, 64, 2, false", True),
+              ("1, 4, 2, 3, 32, 2, false", False), ("2, 2, 1, 2, 64, 3, true", False), ("4, 2, 1, 2, 64, 4, true", False),
+              ("4, 2, 1, 2, 32, 2, true", False), ("2, 2, 2, 2, 32, 2, false", False)]
+
+
+def test_wgrad_plan_names_are_the_compiled_kernels(tmp_path):
+    """every kernel name yh_conv_wgrad_info reports for a descriptor it accepts (the reduced corpus of tools/wgrad_plan_table.py) is a
+    kernel symbol of the built library, every conv_wgrad_kernel instantiation in the code object of conv_wgrad.hip is reported for
+    some descriptor (no dead instantiation), and that code object holds exactly the known instantiations and wgrad_reduce_kernel.
+    Symbols are listed (llvm-objdump -t), nothing is disassembled."""
+    import subprocess
+    from test_isa_packed_forms import OBJDUMP, _code_objects
+    from yoloseries_amd import _lib
+    if not os.path.exists(OBJDUMP):
+        import pytest
+        pytest.skip("llvm-objdump of the ROCm toolchain not found")
+    mod = _wgrad_plan_table()
+    L = _lib.lib()
+    reported = set()
+    for _, c in mod.reduced_cases():
+        rc, _, name = mod.info(L, mod.make_desc(L, c))[:3]
+        if rc == 0:
+            reported.add(name)
+    kernels, own = set(), None
+    for i, blob in enumerate(_code_objects(_lib.LIB_PATH)):
+        f = tmp_path / f"co_{i}.elf"
+        f.write_bytes(blob)
+        syms = subprocess.run([OBJDUMP, "-t", "-C", str(f)], stdout=subprocess.PIPE, text=True, check=True).stdout
+        names = {m.group(1) for m in re.finditer(r" F \.text\s+\S+\s+(?:\.protected )?(?:void )?(?:\(anonymous namespace\)::)?(\w+(?:<[^>]*>)?)\(", syms)}
+        kernels |= names
+        if "wgrad_reduce_kernel" in names:
+            own = names
+    assert own is not None, "no code object with wgrad_reduce_kernel"
+    assert reported and reported <= kernels, sorted(reported - kernels)
+    want = {f"conv_wgrad_kernel<{a}, false>" for a, _ in WGRAD_ROWS} | {f"conv_wgrad_kernel<{a}, true>" for a, fused in WGRAD_ROWS if fused}
+    assert own == want | {"wgrad_reduce_kernel"}, (sorted(own - want), sorted(want - own))
+    assert want <= reported, sorted(want - reported)
+
+
+def test_wgrad_tuner_candidates():
+    """the (tile_k, splits) candidates the engine times for a weight gradient (Program._wgrad_candidates: the library's plan says
+    which requests it would honour) for one layer per tiling, patch- and wave-eligible layers and the fused stem, without / with a
+    workspace: the lists the tuner produced when it matched kernel names instead"""
+    from yoloseries_amd._lib import lib
+    from yoloseries_amd.engine.tune import TunerMixin
+    mod = _wgrad_plan_table()
+    L = lib()
+    #        N, ldg, C, ld, ups, Ctot, B, Ho, Wo, Hi, Wi, k, stride, pad | bn_z | tile_k candidates without, with a workspace
+    layers = [((32, 32, 32, 64, 0, 32, 64, 160, 160, 160, 160, 1, 1, 0), 0, (0, 64, 40), (0, 64)),               # <1, 5, 1, 1>, patch-eligible
+              ((32, 32, 192, 192, 0, 192, 64, 80, 80, 80, 80, 1, 1, 0), 0, (0, 64), (0, 64)),                    # <1, 4, 1, 2>
+              ((32, 32, 32, 32, 0, 32, 64, 160, 160, 160, 160, 3, 1, 1), 0, (0, 64, 40), (0, 64)),               # <1, 4, 1, 3>
+              ((128, 128, 128, 128, 0, 128, 64, 160, 160, 160, 160, 1, 1, 0), 0, (0, 64, 128, 129), (0, 64, 128, 129)),     # <1, 4, 2, 1>, wave-eligible
+              ((128, 128, 256, 256, 0, 256, 64, 40, 40, 40, 40, 1, 1, 0), 0, (0, 64, 128, 129), (0, 64, 128, 129)),         # <1, 4, 2, 2>
+              ((192, 192, 384, 384, 0, 384, 64, 40, 40, 40, 40, 1, 1, 0), 0, (0, 128, 129), (0, 128, 129)),      # <1, 4, 2, 3>
+              ((64, 64, 64, 64, 0, 64, 64, 160, 160, 160, 160, 3, 1, 1), 0, (0, 40, 129), (0, 129)),             # <2, 2, 1, 2>
+              ((1024, 1024, 1024, 1024, 0, 1024, 64, 20, 20, 20, 20, 1, 1, 0), 0, (0, 32, 35, 129), (0, 32, 35, 129)),      # <4, 2, 1, 2>
+              ((96, 96, 48, 48, 0, 48, 64, 160, 160, 320, 320, 3, 2, 1), 0, (0, 32, 35), (0, 32, 35)),           # ... 48 channels: no wave form
+              ((32, 32, 16, 16, 0, 16, 64, 320, 320, 320, 320, 3, 1, 1), 1, (0, 64, 40), (0, 64)),               # fused stem, N <= 32
+              ((48, 48, 16, 16, 0, 16, 64, 320, 320, 320, 320, 3, 1, 1), 1, (0, 64, 40), (0, 64))]               # fused stem, N > 32
+    got = {}
+    for f, bn, without, with_ws in layers:
+        for ws, want in ((0, without), (1, with_ws)):
+            c = mod.case_of_key("wgrad11f" if bn else "wgrad11", f)
+            c["ws"] = ws
+            wd = mod.make_desc(L, c)
+            M, ntile = wd.B * wd.Ho * wd.Wo, L.yh_conv_wgrad_tiles(wd.N, wd.KH * wd.KW * wd.seg.C)
+            wd.tile_k, wd.splits = 7, 11
+            cands = TunerMixin._wgrad_candidates(L, wd, M, ntile)
+            assert (wd.tile_k, wd.splits) == (7, 11)          # the enumeration leaves the descriptor as it was
+            assert tuple(tk for tk, _ in cands) == want, (f, ws, cands)
+            got[f[0], f[11], ws] = dict(cands)
+    assert got[1024, 1, 0] == {0: [4, 8, 12, 16, 24], 32: [4, 8, 12, 16, 24], 35: [4, 8, 12, 16, 24], 129: [64, 96, 192]}
+    assert got[192, 1, 1] == {0: [86, 171, 256, 342, 400], 128: [43, 86, 128, 171, 256], 129: [96, 192]}
+    assert got[64, 3, 0] == {0: [52, 103, 154, 205, 308], 40: [1024], 129: [125, 128, 255, 256]}
+
+
+def test_wgrad_refusals_agree_between_plan_query_and_launcher():
+    """every argument check of yh_conv_wgrad, one descriptor each with exactly that field broken: yh_conv_wgrad_info and
+    yh_conv_wgrad return the same non-zero rc and name the same check.  The operands are fake addresses — the launcher is called
+    only after the query has refused the descriptor (both read one plan: it refuses before anything is launched)"""
+    import ctypes as C
+    from yoloseries_amd import _lib
+    mod = _wgrad_plan_table()
+    L = _lib.lib()
+    base = dict(N=32, ldg=32, C=16, ld=16, ups=0, coff_k=0, Ctot=16, B=2, Ho=12, Wo=20, Hi=12, Wi=20, KH=3, stride=1, pad=1, splits=3,
+                tile_k=0, bn=0, ws=0)
+
+    def desc(**kw):
+        ptrs = {k: kw.pop(k) for k in list(kw) if k in ("gy", "ptr", "dw", "partial", "partial_bytes", "bn_ldz", "bn_ws")}
+        d = mod.make_desc(L, dict(base, **kw))
+        for k, v in ptrs.items():
+            setattr(d.seg if k == "ptr" else d, k, v)
+        return d
+    o = _lib.WgradInfo()
+    ok = desc()
+    assert L.yh_conv_wgrad_info(C.byref(ok), C.byref(o)) == 0 and o.name == b"conv_wgrad_kernel<1, 5, 1, 1, 32, 3, true, false>"
+    assert L.yh_conv_wgrad_info(C.byref(desc(tile_k=40)), C.byref(o)) == 0 and o.form == _lib.YH_WGRAD_PATCH
+    one_pixel = dict(KH=1, pad=0, C=8, ld=8, Ctot=8, N=8)
+    broken = [
+        ("null desc / bad dims", None),
+        ("null desc / bad dims", desc(B=0)),
+        ("null desc / bad dims", desc(Wi=0)),
+        ("workspace too small / unaligned", desc(ws=3)),                      # 4 bytes short
+        ("workspace too small / unaligned", desc(ws=1, partial=8 * mod.P + 4)),
+        ("workspace too small / unaligned", desc(ws=3, tile_k=129, N=64, C=32, ld=32, Ctot=32, ldg=64, Ho=16, Hi=16)),     # the wave form's slots
+        ("bad operands", desc(tile_k=40, gy=mod.P + 2)),                      # patch form
+        ("bad operands", desc(tile_k=40, dw=None)),
+        ("a single image needs a 2 GiB operand", desc(**one_pixel, B=1, Ho=4096, Wo=4096, Hi=4096, Wi=4096, ldg=64)),
+        ("gy null/unaligned", desc(gy=None)),
+        ("gy null/unaligned", desc(ldg=36)),
+        ("needs ldg padded to 8", desc(N=28, ldg=24)),
+        ("segment misaligned", desc(C=12, Ctot=12)),
+        ("segment misaligned", desc(ptr=None)),
+        ("bad channel offset", desc(coff_k=8)),
+        ("bad stride", desc(stride=3)),
+        ("bad kernel size", desc(KH=9, pad=4)),
+        ("geometry mismatch", desc(Hi=13)),
+        ("dw null / bad splits", desc(dw=None)),
+        ("dw null / bad splits", desc(splits=0)),
+        ("upsampled segment needs even dims", desc(ups=1, Ho=13, Hi=13)),
+        ("too many pixels", desc(**dict(one_pixel, ld=0), ldg=0, B=1 << 15, Ho=256, Wo=256, Hi=256, Wi=256)),
+        ("operands of 2 GiB or more", desc(N=1 << 30, ldg=0)),
+        ("too many splits", desc(B=64, Ho=184, Wo=184, Hi=184, Wi=184, splits=70000)),       # 67 712 splits of 32 pixels hold pixels
+        ("fused BatchNorm backward (bn_z) needs a wide tiling", desc(bn=1, C=32, ld=32, Ctot=32)),          # <1, 4, 1, 3>: not fused
+        ("fused BatchNorm backward (bn_z) needs a wide tiling", desc(bn=1, N=64, ldg=64, C=8, ld=8, Ctot=8)),      # <1, 4, 2, 1>
+        ("bad fused-BatchNorm operands", desc(bn=1, bn_ldz=24)),
+        ("bad fused-BatchNorm operands", desc(bn=1, bn_ws=None)),
+        ("bn_z of 2 GiB or more", desc(bn=1, bn_ldz=1 << 22)),
+    ]
+    for what, d in broken:
+        ref = C.byref(d) if d is not None else None
+        rc = L.yh_conv_wgrad_info(ref, C.byref(o))
+        msg = L.yh_last_error().decode()
+        assert rc != 0 and what in msg, (what, rc, msg)
+        assert L.yh_conv_wgrad(ref, None) == rc and L.yh_last_error().decode() == msg, (what, L.yh_last_error())
 
 
 def test_executor_knows_every_program_entry_point():

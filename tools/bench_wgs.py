@@ -7,6 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from yoloseries_amd import hipk
 from yoloseries_amd._lib import lib
+from yoloseries_amd.engine import Program
 
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -44,17 +45,15 @@ for name, H, Cin, Cout, k, s in shapes:
     gy = torch.randn(B, Ho, Ho, Cout, device=dev).to(torch.bfloat16)
     dw = torch.zeros(Cout, k * k * Cin, device=dev)
     fl = 2.0 * M * Cout * Cin * k * k
+    d = hipk.wgrad_desc(hipk.full(gy), Cout, hipk.full(x), 0, Cin, B, Ho, Ho, H, H, k, s, p, dw, 1)
     cands = []
     for tk in (0, 32, 35, 128):
-        if tk == 128 and not (128 <= k * k * Cin <= 384):
+        plan = Program._wgrad_info(L, d, tk)
+        if plan.tile_k != tk:                # a request the library would ignore (32 / 35: the general 128 x 128 tiling only)
             continue
-        if tk in (32, 35) and not L.yh_conv_wgrad_kernel_name(Cout, k * k * Cin).decode().startswith("conv_wgrad_kernel<4, 2, 1, 2, 64"):
-            continue
-        nt = L.yh_conv_wgrad_tiles2(Cout, k * k * Cin, tk)
         for tot in (256, 512, 768, 1024):
-            sp = max(1, min((M + 255) // 256, (tot + nt - 1) // nt))
+            sp = max(1, min((M + 255) // 256, (tot + plan.tiles - 1) // plan.tiles))
             cands.append((tk, sp))
-    d = hipk.wgrad_desc(hipk.full(gy), Cout, hipk.full(x), 0, Cin, B, Ho, Ho, H, H, k, s, p, dw, 1)
     d.tile_k = 129
     T = L.yh_conv_wgrad_wave_tiles(C.byref(d))
     if T > 0:

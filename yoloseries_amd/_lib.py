@@ -52,6 +52,15 @@ class WgradDesc(C.Structure):
     ]
 
 
+class WgradInfo(C.Structure):
+    """yh_wgrad_info: what yh_conv_wgrad launches for a descriptor (yh_conv_wgrad_info)"""
+    _fields_ = [("form", C.c_int32), ("tiles", C.c_int32), ("splits", C.c_int32), ("tile_k", C.c_int32), ("ws_bytes", C.c_uint64),
+                ("name", C.c_char * 96)]
+
+
+YH_WGRAD_IM2COL, YH_WGRAD_PATCH, YH_WGRAD_WAVE = 0, 1, 2
+
+
 class V5LossDesc(C.Structure):
     _fields_ = [
         ("B", C.c_int32), ("maxbox", C.c_int32), ("num_class", C.c_int32), ("num_anchor", C.c_int32),
@@ -138,8 +147,7 @@ _SIGS = {
     "yh_conv_wgrad_wave_name": (C.c_char_p, [C.POINTER(WgradDesc)]),
     "yh_conv_wgrad_tiles": (_i32, [_i32, _i32]),
     "yh_conv_wgrad_tiles2": (_i32, [_i32, _i32, _i32]),
-    "yh_conv_wgrad_kernel_name": (C.c_char_p, [_i32, _i32]),
-    "yh_conv_wgrad_kernel_name2": (C.c_char_p, [_i32, _i32, _i32]),
+    "yh_conv_wgrad_info": (_i32, [C.POINTER(WgradDesc), C.POINTER(WgradInfo)]),
     "yh_conv_bnr_rows": (_i32, [C.POINTER(ConvDesc)]),
     "yh_conv_kernel_name": (_i32, [C.POINTER(ConvDesc), C.c_char_p, _i32]),
     "yh_bn_finalize": (_i32, [_vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp]),

@@ -10,13 +10,14 @@
 // loads: per-lane offsets are fixed per thread, the walk along the pixels is a scalar offset, rows past
 // the split and padding taps carry an out-of-range offset (hardware zero fill, no branches).
 // The pixel reduction is split over blockIdx.y; partial tiles are added with fp32 atomics (two
-// 128-byte row segments per wave instruction).  Tilings:
-//   wide    (K <= 384: stem, 3x3x32 and most 1x1 layers) one block covers ALL im2col columns, so gy
-//           is read once and the 9 taps of a pixel are gathered by the same block (L1/L2 hits);
-//   general 128 x 128 (8 waves) or 64 x 128 tiles, 64 pixels per k-step, one column tile per block.
+// 128-byte row segments per wave instruction), or go to a workspace and are summed in split order.  The instantiations are the
+// rows of ONE table (WG_ROWS); wg_plan decides once per call what is launched — form, row, splits, grid — and the launcher and
+// every query (yh_conv_wgrad_info, _ws_bytes, _tiles ...) read that plan.  Tilings: see wg_tiling.
 // Replaces autograd's conv weight gradient (train_yolov5.py:337).
 #include "common.h"
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -396,119 +397,158 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* __restr
     }
 }
 
-template <int WN, int WC, int TNW, int TCW, int TK>
-constexpr size_t wg_smem() {
-    // tiles [2][TK][PA + PB] + (fused BatchNorm backward) the per-channel constants [5][TN]
-    return (size_t)2 * TK * (wg_pitch(WN * TNW * 32) + wg_pitch(WC * TCW * 32)) * 2 + 5 * WN * TNW * 32 * 4;
+// tiles [2][TK][PA + PB] + (fused BatchNorm backward) the per-channel constants [5][TN]
+constexpr size_t wg_smem(int TN, int TCOLS, int TK) { return (size_t)2 * TK * (wg_pitch(TN) + wg_pitch(TCOLS)) * 2 + 5 * TN * 4; }
+
+template <int WN, int WC, int TNW, int TCW, int TK, int MINW, bool PF2, bool FBN>
+void wg_launch(const WgK& k, dim3 grid, hipStream_t st)
+{
+    conv_wgrad_kernel<WN, WC, TNW, TCW, TK, MINW, PF2, FBN><<<grid, dim3(WN * WC * 64), wg_smem(WN * TNW * 32, WC * TCW * 32, TK), st>>>(k);
+}
+typedef void (*WgLaunch)(const WgK&, dim3, hipStream_t);
+// (a row without the fused form must not instantiate it)
+template <int WN, int WC, int TNW, int TCW, int TK, int MINW, bool PF2, bool HAS_FBN>
+constexpr WgLaunch wg_fused()
+{
+    if constexpr (HAS_FBN) return &wg_launch<WN, WC, TNW, TCW, TK, MINW, PF2, true>;
+    else return nullptr;
 }
 
-// instantiation used for a layer (N out channels, Kseg im2col columns of the segment)
-// tile_k == 128 asks for the general 128-column tiling on a layer that would get a wide one (64 x Kseg tiles): measured 17-29 %
-// faster on 1x1 layers with >= 128 channels on both sides (fewer re-reads of gy / x per tile, half the blocks per output element)
-bool wg_wide(int Kseg, int tile_k) { return Kseg <= 384 && !(tile_k == 128 && Kseg >= 128); }
-int wg_config(int N, int Kseg, int tile_k)
+// THE instantiation table: every conv_wgrad_kernel the library holds is one row — WN x WC waves of (TNW*32) x (TCW*32), TK pixels
+// per k-step, MINW blocks per CU asked of the compiler, PF2 (two tiles in flight), and whether the row also exists with the
+// BatchNorm-backward apply fused into its A-operand loader (bn_z: the wide tilings a stem layer gets).  The launch, the LDS size,
+// the tile's rows and columns and the profiler name all come from the row.  On the general 128-column tiling (W6: 82 KB of LDS, ONE
+// block per CU whose every k-step ends in a block-wide barrier) tile_k 32 keeps the waves on 32-pixel k-steps (41 KB: two blocks
+// per CU, one block's barrier is covered by the other's MFMAs: +10 % on the 3x3 layers of YOLOv5s at 40 x 40) and tile_k 35 takes
+// FOUR waves of 64 x 64 on 32-pixel k-steps (two transposing reads per MFMA instead of three: +15 % at 20 x 20).  Measured and
+// dropped: three blocks per CU (equal), the 4-wave tile with two register sets in flight (spills: half the speed).
+//        id       WN WC TNW TCW TK MINW PF2    fused
+#define WG_ROWS(X)                                                                                                       \
+    X(W0S,     1, 5, 1, 1, 32, 3, true,  true)    /* N <= 32, <= 160 columns (stem: 144 of 160 used) */                    \
+    X(W0S_64,  1, 5, 1, 1, 64, 3, true,  true)                                                                            \
+    X(W0,      1, 4, 1, 2, 32, 3, true,  true)    /* N <= 32, <= 256 columns */                                            \
+    X(W0_64,   1, 4, 1, 2, 64, 2, true,  true)                                                                            \
+    X(W1,      1, 4, 1, 3, 32, 3, false, false)   /* N <= 32, <= 384 columns */                                            \
+    X(W1_64,   1, 4, 1, 3, 64, 2, false, false)                                                                           \
+    X(W2,      1, 4, 2, 1, 32, 4, false, false)   /* N > 32, <= 128 columns */                                             \
+    X(W2_64,   1, 4, 2, 1, 64, 2, false, false)                                                                           \
+    X(W3,      1, 4, 2, 2, 32, 3, false, true)    /* N > 32, <= 256 columns */                                             \
+    X(W3_64,   1, 4, 2, 2, 64, 2, false, true)                                                                            \
+    X(W4,      1, 4, 2, 3, 32, 2, false, false)   /* N > 32, <= 384 columns */                                             \
+    X(W5,      2, 2, 1, 2, 64, 3, true,  false)   /* general, N <= 64: 64 x 128 */                                         \
+    X(W6,      4, 2, 1, 2, 64, 4, true,  false)   /* general: 128 x 128, 8 waves of 32 x 64 */                             \
+    X(W6_32,   4, 2, 1, 2, 32, 2, true,  false)   /* ... tile_k 32 */                                                      \
+    X(W6_35,   2, 2, 2, 2, 32, 2, false, false)   /* ... tile_k 35 */
+
+struct WgRow {
+    int WN, WC, TNW, TCW, TK, MINW;
+    bool PF2;
+    WgLaunch plain, fused;
+    int rows() const { return WN * TNW * 32; }
+    int cols() const { return WC * TCW * 32; }
+};
+#define WG_ID(ID, ...) ID,
+enum WgRowId { WG_ROWS(WG_ID) };
+#define WG_ROW(ID, WN, WC, TNW, TCW, TK, MINW, PF2, HF) \
+    {WN, WC, TNW, TCW, TK, MINW, PF2, &wg_launch<WN, WC, TNW, TCW, TK, MINW, PF2, false>, wg_fused<WN, WC, TNW, TCW, TK, MINW, PF2, HF>()},
+const WgRow wg_rows[] = {WG_ROWS(WG_ROW)};
+#undef WG_ID
+#undef WG_ROW
+
+// the instantiation as profilers print it
+void wg_row_name(const WgRow& r, bool fbn, char* out, size_t len)
 {
-    if (wg_wide(Kseg, tile_k)) {
-        if (N <= 32) return Kseg <= 256 ? 0 : 1;
-        return Kseg <= 128 ? 2 : (Kseg <= 256 ? 3 : 4);
+    snprintf(out, len, "conv_wgrad_kernel<%d, %d, %d, %d, %d, %d, %s, %s>", r.WN, r.WC, r.TNW, r.TCW, r.TK, r.MINW, r.PF2 ? "true" : "false",
+             fbn ? "true" : "false");
+}
+
+enum WgForm { WG_IM2COL = 0, WG_PATCH = 1, WG_WAVE = 2 };
+
+// Everything yh_conv_wgrad decides for a descriptor, decided once (wg_plan); the launcher and every query read it.
+struct WgPlan {
+    bool shaped;                 // the fields below are filled (the descriptor's dims are positive)
+    int form;                    // WgForm
+    bool honoured;               // the request in tile_k changed the launch (an ignored one launches what tile_k 0 does)
+    int tiles;                   // of the form taken: ntiles * ctiles, the wave form's 128 x 128 tiles
+    size_t ws_bytes;             // workspace (yh_wgrad_desc.partial) of the form taken
+    // im2col form (conv_wgrad_kernel)
+    const WgRow* row;
+    int ntiles, ctiles;          // tiles along the out channels / the im2col columns
+    int TK, rows_per_split, splits;      // pixels per k-step; the split of the pixels in whole k-steps; the splits that are not empty
+    dim3 grid;
+    bool fbn;
+    WgK k;                       // (filled by wg_plan_launch)
+    // batch split: bytes of gy / of the input segment per image, images per launch (>= B: one launch)
+    unsigned long gy_img, x_img;
+    int chunk;
+};
+
+// The im2col tiling of a layer (N out channels, Kseg im2col columns of the segment):
+//   wide    (Kseg <= 384: stem, 3x3x32 and most 1x1 layers) one block covers ALL im2col columns, so gy is read once and the 9 taps
+//           of a pixel are gathered by the same block (L1/L2 hits); 32 pixels per k-step (more resident blocks), or 64 where asked
+//           for (tile_k 64: half the barriers and twice the loads in flight per thread; the engine times both per layer);
+//   general 128 x 128 (8 waves) or 64 x 128 tiles, one column tile per block.  tile_k 128 asks for it on a layer that would get a
+//           wide tiling: measured 17-29 % faster on 1x1 layers with >= 128 channels on both sides (fewer re-reads of gy / x per
+//           tile, half the blocks per output element)
+void wg_tiling(int N, int Kseg, int tile_k, WgPlan* pl)
+{
+    const bool wide = Kseg <= 384 && !(tile_k == 128 && Kseg >= 128);
+    const bool k64 = tile_k == 64;
+    WgRowId r;
+    pl->honoured = tile_k == 128 && !wide && Kseg <= 384;
+    if (wide) {
+        if (N <= 32) r = Kseg <= 160 ? (k64 ? W0S_64 : W0S) : Kseg <= 256 ? (k64 ? W0_64 : W0) : (k64 ? W1_64 : W1);
+        else         r = Kseg <= 128 ? (k64 ? W2_64 : W2) : Kseg <= 256 ? (k64 ? W3_64 : W3) : W4;
+        if (k64 && r != W4) pl->honoured = true;
+    } else if (N <= 64) r = W5;
+    else {
+        r = tile_k == 32 ? W6_32 : tile_k == 35 ? W6_35 : W6;
+        if (r != W6) pl->honoured = true;
     }
-    return N <= 64 ? 5 : 6;
+    pl->row = &wg_rows[r];
+    pl->TK = pl->row->TK;
+    pl->ntiles = (N + pl->row->rows() - 1) / pl->row->rows();
+    pl->ctiles = (Kseg + pl->row->cols() - 1) / pl->row->cols();
 }
-const char* const wg_names[7] = {
-    "conv_wgrad_kernel<1, 4, 1, 2, 32, 3, true, false>", "conv_wgrad_kernel<1, 4, 1, 3, 32, 3, false, false>", "conv_wgrad_kernel<1, 4, 2, 1, 32, 4, false, false>",
-    "conv_wgrad_kernel<1, 4, 2, 2, 32, 3, false, false>", "conv_wgrad_kernel<1, 4, 2, 3, 32, 2, false, false>", "conv_wgrad_kernel<2, 2, 1, 2, 64, 3, true, false>",
-    "conv_wgrad_kernel<4, 2, 1, 2, 64, 4, true, false>"};
 
-}  // namespace
-
-/* name of the kernel instantiation yh_conv_wgrad launches for a layer, as profilers print it */
-extern "C" const char* yh_conv_wgrad_kernel_name2(int N, int Kseg, int tile_k)
+// What a launch for d would be: tiling, split of the pixels, form, workspace.  Arithmetic on the dims alone (false where one is not
+// positive) — it refuses nothing and looks at no operand: yh_conv_wgrad_ws_bytes answers from it, also for what a launch refuses.
+bool wg_shape(const yh_wgrad_desc* d, WgPlan* pl)
 {
-    const int c = wg_config(N, Kseg, tile_k);
-    if (c == 6 && tile_k == 32) return "conv_wgrad_kernel<4, 2, 1, 2, 32, 2, true, false>";
-    if (c == 6 && tile_k == 35) return "conv_wgrad_kernel<2, 2, 2, 2, 32, 2, false, false>";
-    return (c == 0 && Kseg <= 160) ? "conv_wgrad_kernel<1, 5, 1, 1, 32, 3, true, false>" : wg_names[c];
-}
-extern "C" const char* yh_conv_wgrad_kernel_name(int N, int Kseg) { return yh_conv_wgrad_kernel_name2(N, Kseg, 0); }
-/* 1 if the patch form (tile_k 40, conv_wgp_kernel) applies to this descriptor */
-extern "C" int yh_conv_wgrad_patch_ok(const yh_wgrad_desc* d) { return d ? yh_wgp_ok(d) : 0; }
-/* tile_k 129 (conv_wgs_kernel): number of 128 x 128 tiles of the layer, 0 when the form does not apply; its profiler name */
-extern "C" int yh_conv_wgrad_wave_tiles(const yh_wgrad_desc* d) { return d ? yh_wgs_tiles(d) : 0; }
-extern "C" const char* yh_conv_wgrad_wave_name(const yh_wgrad_desc* d) { return d ? yh_wgs_name(d) : ""; }
-
-/* tile the kernel will use for a layer: rows (out channels) x im2col columns per block; used by the host to size `splits` */
-extern "C" int yh_conv_wgrad_tiles2(int N, int Kseg, int tile_k)
-{
-    if (wg_wide(Kseg, tile_k)) return N <= 32 ? (N + 31) / 32 : (N + 63) / 64;
-    const int tn = N <= 64 ? 64 : 128;
-    return ((N + tn - 1) / tn) * ((Kseg + 127) / 128);
-}
-extern "C" int yh_conv_wgrad_tiles(int N, int Kseg) { return yh_conv_wgrad_tiles2(N, Kseg, 0); }
-
-static int conv_wgrad_launch(const yh_wgrad_desc* d, yh_stream stream);
-
-// pixels per k-step / effective split count of a launch (shared by the launcher and the workspace query)
-static void wg_split_plan(const yh_wgrad_desc* d, long M, int* tk_out, int* rps_out, int* splits_out)
-{
+    pl->shaped = false;
+    pl->form = WG_IM2COL;
+    pl->ws_bytes = 0;
+    if (!d || d->B <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->N <= 0 || d->seg.C <= 0 || d->KH <= 0 || d->KW <= 0) return false;
     const int Kseg = d->KH * d->KW * d->seg.C;
-    const bool wide = wg_wide(Kseg, d->tile_k);
-    const int cfg = wg_config(d->N, Kseg, d->tile_k);
-    const bool tk64 = wide && d->tile_k == 64 && cfg <= 3;
-    const int TK = ((wide && !tk64) || (cfg == 6 && (d->tile_k == 32 || d->tile_k == 35))) ? 32 : 64;
-    int splits = d->splits < 1 ? 1 : d->splits;
-    int rps = (int)((M + splits - 1) / splits);
-    rps = ((rps + TK - 1) / TK) * TK;
-    splits = (int)((M + rps - 1) / rps);
-    *tk_out = TK; *rps_out = rps; *splits_out = splits;
-}
-
-/* bytes of workspace (yh_wgrad_desc.partial) a launch with these dims / splits / tile_k needs for the plain-store partial tiles:
- * the form the launch will take decides — tile_k 129 where conv_wgs_kernel is eligible: its G + T - 1 slots of 64 KB; every other
- * launch (the patch form and the fused stem backward have no workspace form: they go through conv_wgrad_kernel's): split-M tiles */
-extern "C" size_t yh_conv_wgrad_ws_bytes(const yh_wgrad_desc* d)
-{
-    if (!d || d->B <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->N <= 0 || d->seg.C <= 0 || d->KH <= 0 || d->KW <= 0) return 0;
-    if (d->tile_k == 129 && yh_wgs_ok(d)) return yh_wgs_ws_bytes(d);
+    wg_tiling(d->N, Kseg, d->tile_k, pl);
     const long M = (long)d->B * d->Ho * d->Wo;
-    int tk, rps, splits;
-    wg_split_plan(d, M, &tk, &rps, &splits);
-    const size_t pn = ((size_t)d->N + 7) / 8 * 8, pk = (size_t)d->KH * d->KW * d->seg.C;
-    return (size_t)splits * pn * pk * sizeof(float);
+    // (in long: a descriptor with 2^31 pixels or more is refused by wg_plan_launch, not here)
+    long rps = (M + (d->splits < 1 ? 1 : d->splits) - 1) / (d->splits < 1 ? 1 : d->splits);
+    rps = ((rps + pl->TK - 1) / pl->TK) * pl->TK;
+    const int splits = (int)((M + rps - 1) / rps);
+    pl->rows_per_split = (int)rps;
+    pl->splits = splits;
+    pl->grid = dim3(pl->ntiles * pl->ctiles, (splits + 7) / 8 * 8);
+    pl->fbn = d->bn_z != nullptr;
+    // the form: wave-private tiles + stream-K (conv_wgs.hip) or the patch form (conv_wgp.hip) where asked for AND eligible, else im2col.
+    // The patch form and the fused stem backward have no workspace form: with a workspace they are not eligible / go through
+    // conv_wgrad_kernel's split-M tiles, whose size is also what is answered for a patch launch (it takes no workspace)
+    pl->form = WG_IM2COL;
+    pl->tiles = pl->ntiles * pl->ctiles;
+    pl->ws_bytes = (size_t)splits * (((size_t)d->N + 7) / 8 * 8) * ((size_t)d->KH * d->KW * d->seg.C) * sizeof(float);
+    const int wtiles = d->tile_k == 129 ? yh_wgs_tiles(d) : 0;
+    if (wtiles > 0) {
+        pl->form = WG_WAVE;
+        pl->tiles = wtiles;
+        pl->ws_bytes = yh_wgs_ws_bytes(d);      // its G + T - 1 slots of 64 KB
+    } else if (d->tile_k == 40 && yh_wgp_ok(d)) pl->form = WG_PATCH;
+    if (pl->form != WG_IM2COL) pl->honoured = true;
+    return pl->shaped = true;
 }
 
-/* The kernels address gy and the input segment with 32-bit buffer offsets.  A launch whose operands reach 2 GiB is split over the
- * batch: every part is a launch of its own on a sub-range of images (pointers advanced, dw accumulated by the same atomics). */
-extern "C" int yh_conv_wgrad(const yh_wgrad_desc* d, yh_stream stream)
-{
-    YH_CHECK_ARG(d != nullptr && d->B > 0 && d->Ho > 0 && d->Wo > 0 && d->Hi > 0 && d->Wi > 0, "yh_conv_wgrad: null desc / bad dims");
-    const unsigned long gy_img = (unsigned long)d->Ho * d->Wo * d->ldg * 2;
-    const unsigned long x_img = (unsigned long)(d->Hi >> d->seg.ups) * (d->Wi >> d->seg.ups) * d->seg.ld * 2;
-    const unsigned long lim = (1ul << 31) - 4096;
-    if (d->partial) YH_CHECK_ARG(yh_aligned16(d->partial) && d->partial_bytes >= yh_conv_wgrad_ws_bytes(d), "yh_conv_wgrad: workspace too small / unaligned");
-    if (d->tile_k == 129 && yh_wgs_ok(d)) return yh_wgs_run(d, stream);   // wave-private tiles + stream-K (conv_wgs.hip), else the forms below
-    if (d->tile_k == 40 && yh_wgp_ok(d)) {          // patch form (conv_wgp.hip) where it is eligible, else the im2col form below
-        YH_CHECK_ARG(d->gy && yh_aligned16(d->gy) && d->ldg % 8 == 0 && d->seg.ptr && yh_aligned16(d->seg.ptr) && d->seg.ld % 8 == 0 && d->dw &&
-                     d->coff_k % 8 == 0 && d->coff_k + d->seg.C <= d->Ctot, "yh_conv_wgrad: bad operands");
-        return yh_wgp_run(d, stream);
-    }
-    if (gy_img * d->B < lim && x_img * d->B < lim) return conv_wgrad_launch(d, stream);
-    const unsigned long per = gy_img > x_img ? gy_img : x_img;
-    YH_CHECK_ARG(per < lim, "yh_conv_wgrad: a single image needs a 2 GiB operand");
-    const int chunk = (int)(lim / per);
-    const int parts = (d->B + chunk - 1) / chunk;
-    for (int b0 = 0; b0 < d->B; b0 += chunk) {
-        yh_wgrad_desc p = *d;
-        p.B = d->B - b0 < chunk ? d->B - b0 : chunk;
-        p.gy = d->gy + (size_t)b0 * (gy_img / 2);
-        p.seg.ptr = d->seg.ptr + (size_t)b0 * (x_img / 2);
-        p.splits = (d->splits + parts - 1) / parts;
-        const int rc = conv_wgrad_launch(&p, stream);
-        if (rc != YH_OK) return rc;
-    }
-    return YH_OK;
-}
-
-static int conv_wgrad_launch(const yh_wgrad_desc* d, yh_stream stream)
+// One conv_wgrad_kernel launch — a whole descriptor or one part of a batch split, shaped (wg_shape) by the caller: the launcher's
+// checks, then the kernel parameters.  (A descriptor that passes the checks in front of the first use of the shape has positive dims.)
+int wg_plan_launch(const yh_wgrad_desc* d, WgPlan* pl)
 {
     YH_CHECK_ARG(d != nullptr, "yh_conv_wgrad: null desc");
     YH_CHECK_ARG(d->gy && yh_aligned16(d->gy) && d->ldg % 8 == 0, "yh_conv_wgrad: gy null/unaligned");
@@ -521,9 +561,9 @@ static int conv_wgrad_launch(const yh_wgrad_desc* d, yh_stream stream)
                  "yh_conv_wgrad: geometry mismatch");
     YH_CHECK_ARG(d->dw != nullptr && d->splits >= 1, "yh_conv_wgrad: dw null / bad splits");
     if (d->seg.ups) YH_CHECK_ARG(d->Hi % 2 == 0 && d->Wi % 2 == 0, "yh_conv_wgrad: upsampled segment needs even dims");
-    long M = (long)d->B * d->Ho * d->Wo;
+    const long M = (long)d->B * d->Ho * d->Wo;
     YH_CHECK_ARG(M < (1L << 31) - 256, "yh_conv_wgrad: too many pixels");
-    WgK k;
+    WgK& k = pl->k;
     k.d = *d;
     k.M = (int)M;
     k.Ktot = d->KH * d->KW * d->Ctot;
@@ -535,35 +575,14 @@ static int conv_wgrad_launch(const yh_wgrad_desc* d, yh_stream stream)
     k.gybytes = (unsigned)gyb;
     k.xbytes = (unsigned)xb;
     k.pointwise = (d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && !d->seg.ups) ? 1 : 0;
-    hipStream_t st = (hipStream_t)stream;
-    const bool wide = wg_wide(k.Kseg, d->tile_k);
-    // pixels per k-step: 32 for the wide tilings (more resident blocks), 64 when asked for (d->tile_k == 64: half the barriers and
-    // twice the loads in flight per thread; the engine times both per layer) and for the general tiles
-    const int cfg = wg_config(d->N, k.Kseg, d->tile_k);
-    const bool tk64 = wide && d->tile_k == 64 && cfg <= 3;
-    int TK, rps, splits;
-    wg_split_plan(d, M, &TK, &rps, &splits);
-    k.rows_per_split = rps;
-    YH_CHECK_ARG(splits <= 65528, "yh_conv_wgrad: too many splits");
+    k.rows_per_split = pl->rows_per_split;
+    YH_CHECK_ARG(pl->splits <= 65528, "yh_conv_wgrad: too many splits");
     // a single split needs no reduction: its tile goes straight to dw (the atomic form is then a plain add per element)
-    k.part = (d->partial && splits > 1) ? d->partial : nullptr;
+    k.part = (d->partial && pl->splits > 1) ? d->partial : nullptr;
     k.pn = (d->N + 7) / 8 * 8;
     k.pk = k.Kseg;
-#define YH_WG(WN_, WC_, TNW_, TCW_, TK_, MINW_, NT_, PF2_)                                                      \
-    do {                                                                                                        \
-        dim3 grid((NT_) * k.ctiles, (splits + 7) / 8 * 8);                                                      \
-        conv_wgrad_kernel<WN_, WC_, TNW_, TCW_, TK_, MINW_, PF2_><<<grid, dim3(WN_ * WC_ * 64), wg_smem<WN_, WC_, TNW_, TCW_, TK_>(), st>>>(k); \
-    } while (0)
-    // the same with the BatchNorm-backward apply fused into the A-operand loader (bn_z): the wide tilings a stem layer gets
-#define YH_WGF(WN_, WC_, TNW_, TCW_, TK_, MINW_, NT_, PF2_)                                                     \
-    do {                                                                                                        \
-        dim3 grid((NT_) * k.ctiles, (splits + 7) / 8 * 8);                                                      \
-        if (fbn) conv_wgrad_kernel<WN_, WC_, TNW_, TCW_, TK_, MINW_, PF2_, true><<<grid, dim3(WN_ * WC_ * 64), wg_smem<WN_, WC_, TNW_, TCW_, TK_>(), st>>>(k); \
-        else     conv_wgrad_kernel<WN_, WC_, TNW_, TCW_, TK_, MINW_, PF2_><<<grid, dim3(WN_ * WC_ * 64), wg_smem<WN_, WC_, TNW_, TCW_, TK_>(), st>>>(k); \
-    } while (0)
-    const bool fbn = d->bn_z != nullptr;
-    if (fbn) {
-        YH_CHECK_ARG(wide && (cfg == 0 || cfg == 3), "yh_conv_wgrad: the fused BatchNorm backward (bn_z) needs a wide tiling with <= 256 im2col columns "
+    if (pl->fbn) {
+        YH_CHECK_ARG(pl->row->fused != nullptr, "yh_conv_wgrad: the fused BatchNorm backward (bn_z) needs a wide tiling with <= 256 im2col columns "
                      "(N <= 32: <= 256 columns; N > 32: 129..256 columns)");
         YH_CHECK_ARG(yh_aligned16(d->bn_z) && d->bn_ldz % 8 == 0 && d->bn_ldz >= d->N && d->bn_ws && d->bn_gamma && d->bn_coef && d->N % 8 == 0,
                      "yh_conv_wgrad: bad fused-BatchNorm operands");
@@ -571,38 +590,140 @@ static int conv_wgrad_launch(const yh_wgrad_desc* d, yh_stream stream)
         YH_CHECK_ARG(zb < (1ul << 31), "yh_conv_wgrad: bn_z of 2 GiB or more is not supported");
         k.zbytes = (unsigned)zb;
     } else k.zbytes = 0;
-    k.ctiles = wide ? 1 : (k.Kseg + 127) / 128;
-    switch (cfg) {
-    case 0:
-        if (k.Kseg <= 160) { if (tk64) YH_WGF(1, 5, 1, 1, 64, 3, (d->N + 31) / 32, true); else YH_WGF(1, 5, 1, 1, 32, 3, (d->N + 31) / 32, true); }  // stem: 5 waves x one 32-column tile (144 of 160 used)
-        else               { if (tk64) YH_WGF(1, 4, 1, 2, 64, 2, (d->N + 31) / 32, true); else YH_WGF(1, 4, 1, 2, 32, 3, (d->N + 31) / 32, true); }
-        break;
-    case 1: if (tk64) YH_WG(1, 4, 1, 3, 64, 2, (d->N + 31) / 32, false); else YH_WG(1, 4, 1, 3, 32, 3, (d->N + 31) / 32, false); break;
-    case 2: if (tk64) YH_WG(1, 4, 2, 1, 64, 2, (d->N + 63) / 64, false); else YH_WG(1, 4, 2, 1, 32, 4, (d->N + 63) / 64, false); break;
-    case 3: if (tk64) YH_WGF(1, 4, 2, 2, 64, 2, (d->N + 63) / 64, false); else YH_WGF(1, 4, 2, 2, 32, 3, (d->N + 63) / 64, false); break;
-    case 4: YH_WG(1, 4, 2, 3, 32, 2, (d->N + 63) / 64, false); break;
-    case 5: YH_WG(2, 2, 1, 2, 64, 3, (d->N + 63) / 64, true); break;
-    default:
-        // 8 waves of 32 x 64, 64-pixel k-steps: 82 KB of LDS, ONE block per CU whose every k-step ends in a block-wide barrier.
-        // tile_k == 32: the same waves on 32-pixel k-steps (41 KB: two blocks per CU, one block's barrier is covered by the other's
-        // MFMAs: +10 % on the 3x3 layers of YOLOv5s at 40 x 40); tile_k == 35: FOUR waves of 64 x 64 on 32-pixel k-steps (two
-        // transposing reads per MFMA instead of three: +15 % at 20 x 20).  Measured and dropped: three blocks per CU (equal), the
-        // 4-wave tile with two register sets in flight (spills: half the speed).  The engine times the three per layer.
-        if (d->tile_k == 32)      YH_WG(4, 2, 1, 2, 32, 2, (d->N + 127) / 128, true);
-        else if (d->tile_k == 35) YH_WG(2, 2, 2, 2, 32, 2, (d->N + 127) / 128, false);
-        else                      YH_WG(4, 2, 1, 2, 64, 4, (d->N + 127) / 128, true);
-        break;
+    k.ctiles = pl->ctiles;
+    return YH_OK;
+}
+
+// descriptor of the images [b0, b0 + chunk) of a batch split
+yh_wgrad_desc wg_part(const yh_wgrad_desc* d, const WgPlan& pl, int b0)
+{
+    const int parts = (d->B + pl.chunk - 1) / pl.chunk;
+    yh_wgrad_desc p = *d;
+    p.B = d->B - b0 < pl.chunk ? d->B - b0 : pl.chunk;
+    p.gy = d->gy + (size_t)b0 * (pl.gy_img / 2);
+    p.seg.ptr = d->seg.ptr + (size_t)b0 * (pl.x_img / 2);
+    p.splits = (d->splits + parts - 1) / parts;
+    return p;
+}
+
+/* The plan of yh_conv_wgrad(d): YH_OK and what will be launched, or the rc of the first check that refuses d.  No HIP call, no
+ * allocation, no operand is dereferenced.  The kernels address gy and the input segment with 32-bit buffer offsets: an im2col
+ * launch whose operands reach 2 GiB is split over the batch — every part is a launch of its own on a sub-range of images (wg_part:
+ * pointers advanced, dw accumulated by the same atomics) with a plan of its own; the first part, which no later one exceeds, is
+ * checked here.  The shape (and with it ws_bytes) is that of the unsplit descriptor.  The wave form's launcher keeps its own
+ * operand checks (yh_wgs_run). */
+int wg_plan(const yh_wgrad_desc* d, WgPlan* pl)
+{
+    wg_shape(d, pl);
+    YH_CHECK_ARG(d != nullptr && d->B > 0 && d->Ho > 0 && d->Wo > 0 && d->Hi > 0 && d->Wi > 0, "yh_conv_wgrad: null desc / bad dims");
+    pl->gy_img = (unsigned long)d->Ho * d->Wo * d->ldg * 2;
+    pl->x_img = (unsigned long)(d->Hi >> d->seg.ups) * (d->Wi >> d->seg.ups) * d->seg.ld * 2;
+    pl->chunk = d->B;
+    const unsigned long lim = (1ul << 31) - 4096;
+    if (d->partial) YH_CHECK_ARG(yh_aligned16(d->partial) && d->partial_bytes >= pl->ws_bytes, "yh_conv_wgrad: workspace too small / unaligned");
+    if (pl->form == WG_WAVE) return YH_OK;
+    if (pl->form == WG_PATCH) {
+        YH_CHECK_ARG(d->gy && yh_aligned16(d->gy) && d->ldg % 8 == 0 && d->seg.ptr && yh_aligned16(d->seg.ptr) && d->seg.ld % 8 == 0 && d->dw &&
+                     d->coff_k % 8 == 0 && d->coff_k + d->seg.C <= d->Ctot, "yh_conv_wgrad: bad operands");
+        return YH_OK;
     }
-#undef YH_WG
-#undef YH_WGF
+    if (pl->gy_img * d->B < lim && pl->x_img * d->B < lim) return wg_plan_launch(d, pl);
+    const unsigned long per = pl->gy_img > pl->x_img ? pl->gy_img : pl->x_img;
+    YH_CHECK_ARG(per < lim, "yh_conv_wgrad: a single image needs a 2 GiB operand");
+    pl->chunk = (int)(lim / per);
+    const yh_wgrad_desc p = wg_part(d, *pl, 0);
+    WgPlan first;
+    wg_shape(&p, &first);
+    return wg_plan_launch(&p, &first);
+}
+
+int conv_wgrad_launch(const WgPlan& pl, hipStream_t st)
+{
+    const WgK& k = pl.k;
+    (pl.fbn ? pl.row->fused : pl.row->plain)(k, pl.grid, st);
     YH_CHECK_LAUNCH("yh_conv_wgrad");
     if (k.part) {
-        const long items = (long)d->N * (k.Kseg / 4);
+        const yh_wgrad_desc& d = k.d;
+        const long items = (long)d.N * (k.Kseg / 4);
         int sg = 1;
-        while (sg < 16 && sg * 8 < splits) sg *= 2;
-        wgrad_reduce_kernel<<<dim3((unsigned)((items + 63) / 64)), dim3(64, sg), 0, st>>>(k.part, splits, k.pn, k.pk, d->N, k.Kseg, d->seg.C, d->Ctot,
-                                                                                        d->coff_k, k.Ktot, d->dw);
+        while (sg < 16 && sg * 8 < pl.splits) sg *= 2;
+        wgrad_reduce_kernel<<<dim3((unsigned)((items + 63) / 64)), dim3(64, sg), 0, st>>>(k.part, pl.splits, k.pn, k.pk, d.N, k.Kseg, d.seg.C, d.Ctot,
+                                                                                        d.coff_k, k.Ktot, d.dw);
         YH_CHECK_LAUNCH("yh_conv_wgrad(reduce)");
+    }
+    return YH_OK;
+}
+
+// the form d would take with tile_k = tk asked: the eligibility queries answer whatever the descriptor's own tile_k says
+int wg_form_for(const yh_wgrad_desc* d, int tk, WgPlan* pl)
+{
+    if (!d) return -1;
+    yh_wgrad_desc q = *d;
+    q.tile_k = tk;
+    return wg_shape(&q, pl) ? pl->form : -1;
+}
+
+}  // namespace
+
+/* 1 if the patch form (tile_k 40, conv_wgp_kernel) applies to this descriptor */
+extern "C" int yh_conv_wgrad_patch_ok(const yh_wgrad_desc* d) { WgPlan pl; return wg_form_for(d, 40, &pl) == WG_PATCH; }
+/* tile_k 129 (conv_wgs_kernel): number of 128 x 128 tiles of the layer, 0 when the form does not apply; its profiler name */
+extern "C" int yh_conv_wgrad_wave_tiles(const yh_wgrad_desc* d) { WgPlan pl; return wg_form_for(d, 129, &pl) == WG_WAVE ? pl.tiles : 0; }
+extern "C" const char* yh_conv_wgrad_wave_name(const yh_wgrad_desc* d) { WgPlan pl; return wg_form_for(d, 129, &pl) == WG_WAVE ? yh_wgs_name(d) : ""; }
+
+/* tiles the im2col kernel will use for a layer: (out channels / rows) x (im2col columns / columns of the tile); used by the host to
+ * size `splits` */
+extern "C" int yh_conv_wgrad_tiles2(int N, int Kseg, int tile_k)
+{
+    WgPlan pl;
+    wg_tiling(N, Kseg, tile_k, &pl);
+    return pl.ntiles * pl.ctiles;
+}
+extern "C" int yh_conv_wgrad_tiles(int N, int Kseg) { return yh_conv_wgrad_tiles2(N, Kseg, 0); }
+
+/* bytes of workspace (yh_wgrad_desc.partial) a launch with these dims / splits / tile_k needs for the plain-store partial tiles:
+ * the form the launch will take decides (WgPlan.ws_bytes).  Answers from the dims alone, also for a descriptor a launch would refuse */
+extern "C" size_t yh_conv_wgrad_ws_bytes(const yh_wgrad_desc* d)
+{
+    WgPlan pl;
+    wg_shape(d, &pl);
+    return pl.ws_bytes;
+}
+
+/* what yh_conv_wgrad(d) will launch (include/yolohip.h): the rc of the launch's checks; `out` is filled from the dims alone, as
+ * yh_conv_wgrad_ws_bytes answers, whenever they are positive */
+extern "C" int yh_conv_wgrad_info(const yh_wgrad_desc* d, yh_wgrad_info* out)
+{
+    YH_CHECK_ARG(out != nullptr, "yh_conv_wgrad_info: null out");
+    memset(out, 0, sizeof(*out));
+    WgPlan pl;
+    const int rc = wg_plan(d, &pl);
+    if (!pl.shaped) return rc;
+    out->form = pl.form;
+    out->tiles = pl.tiles;
+    out->splits = pl.form == WG_IM2COL ? pl.splits : d->splits;      // the other forms clamp the request themselves (WgsPlan.G, WgpPlan.gx)
+    out->tile_k = pl.honoured ? d->tile_k : 0;
+    out->ws_bytes = pl.ws_bytes;
+    if (pl.form == WG_WAVE) snprintf(out->name, sizeof(out->name), "%s", yh_wgs_name(d));
+    else if (pl.form == WG_PATCH) yh_conv_wgrad_patch_name(d, out->name, (int)sizeof(out->name));
+    else wg_row_name(*pl.row, pl.fbn, out->name, sizeof(out->name));
+    return rc;
+}
+
+extern "C" int yh_conv_wgrad(const yh_wgrad_desc* d, yh_stream stream)
+{
+    WgPlan pl;
+    int rc = wg_plan(d, &pl);
+    if (rc != YH_OK) return rc;
+    if (pl.form == WG_WAVE) return yh_wgs_run(d, stream);
+    if (pl.form == WG_PATCH) return yh_wgp_run(d, stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (pl.chunk >= d->B) return conv_wgrad_launch(pl, st);
+    for (int b0 = 0; b0 < d->B; b0 += pl.chunk) {
+        const yh_wgrad_desc p = wg_part(d, pl, b0);
+        WgPlan part;
+        wg_shape(&p, &part);
+        if ((rc = wg_plan_launch(&p, &part)) != YH_OK || (rc = conv_wgrad_launch(part, st)) != YH_OK) return rc;
     }
     return YH_OK;
 }

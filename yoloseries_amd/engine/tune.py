@@ -6,7 +6,7 @@ import os
 
 import torch
 
-from .._lib import YH_CONV_DGRAD, check
+from .._lib import YH_CONV_DGRAD, YH_WGRAD_PATCH, YH_WGRAD_WAVE, WgradInfo, check
 from . import flags as _flags
 
 # the table shipped with the package lives beside the package modules
@@ -89,16 +89,6 @@ def tuning_source():
     """where the launch parameters of this process came from (reported by bench.py)"""
     t = _tune_cache()
     return {"shipped_table": t.hits_shipped, "local_cache": t.hits_local, "timed_now": t.timed}
-
-# wide weight-gradient tilings that also exist with 64-pixel k-steps (yh_wgrad_desc.tile_k = 64): 32-pixel name -> 64-pixel name
-_WGRAD_TK64 = {
-    "conv_wgrad_kernel<1, 5, 1, 1, 32, 3, true, false>": "conv_wgrad_kernel<1, 5, 1, 1, 64, 3, true, false>",
-    "conv_wgrad_kernel<1, 4, 1, 2, 32, 3, true, false>": "conv_wgrad_kernel<1, 4, 1, 2, 64, 2, true, false>",
-    "conv_wgrad_kernel<1, 4, 1, 3, 32, 3, false, false>": "conv_wgrad_kernel<1, 4, 1, 3, 64, 2, false, false>",
-    "conv_wgrad_kernel<1, 4, 2, 1, 32, 4, false, false>": "conv_wgrad_kernel<1, 4, 2, 1, 64, 2, false, false>",
-    "conv_wgrad_kernel<1, 4, 2, 2, 32, 3, false, false>": "conv_wgrad_kernel<1, 4, 2, 2, 64, 2, false, false>",
-}
-
 
 # version prefixes of the tuning-table keys: bumped when the candidates or the meaning of a tuned value change, so that stale
 # entries of a shipped / cached table are not applied.  Stride-2 data gradients carry their own version (conv_dg2_kernel, algo 7,
@@ -212,13 +202,8 @@ class TunerMixin:
         total block count depends on the tile configuration's residency and on how the atomics of the epilogue amortise
         (measured 256..1024 blocks, up to 1.6x apart), so it is timed once per layer when the backward program is built
         (YH_WGRAD_TUNE=0: fixed 512-block rule).  Sets wd.tile_k, returns the split factor."""
-        Kseg = wd.KH * wd.KW * wd.seg.C
-
-        def splits_for(total, tk=0):
-            nt = self.L.yh_conv_wgrad_tiles2(wd.N, Kseg, tk) if tk == 128 else ntile
-            return max(1, min((M + 255) // 256, (total + nt - 1) // nt))
         if os.environ.get("YH_WGRAD_TUNE", "1") == "0":
-            return splits_for(512)
+            return self._wgrad_splits_for(self.L, wd, M, ntile, 512)
         key = f"{KEY_WGRAD_WS if wd.partial else KEY_WGRAD}{'f' if wd.bn_z else ''}:" + ",".join(str(int(v)) for v in (wd.N, wd.ldg, wd.seg.C, wd.seg.ld, wd.seg.ups, wd.Ctot, wd.B, wd.Ho, wd.Wo,
                                                           wd.Hi, wd.Wi, wd.KH, wd.stride, wd.pad))
         cache = _tune_cache()
@@ -230,41 +215,12 @@ class TunerMixin:
         gy_saved = wd.gy
         if not wd.gy:                      # head gradient arrives at run time: time against the scratch buffer
             if self.gy_scratch.numel() < M * wd.ldg:
-                return splits_for(512)
+                return self._wgrad_splits_for(self.L, wd, M, ntile, 512)
             wd.gy = self.gy_scratch.data_ptr()
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        name = self.L.yh_conv_wgrad_kernel_name(wd.N, wd.KH * wd.KW * wd.seg.C).decode()
-        tks = (0, 64) if name in _WGRAD_TK64 else (0,)
-        if name.startswith("conv_wgrad_kernel<4, 2, 1, 2, 64"):
-            tks = tks + (32, 35)            # the general tiling with 32-pixel k-steps (two blocks per CU): 8 waves of 32 x 64 / 4 of 64 x 64
-        if 128 <= Kseg <= 384 and wd.N > 32 and not wd.bn_z:
-            tks = tks + (128,)              # the general 128-column tiling on a layer that defaults to a wide one
         best, best_ms = None, None
-        wd.tile_k = 40
-        if not wd.partial and self.L.yh_conv_wgrad_patch_ok(C.byref(wd)):
-            tks = tks + (40,)               # patch form (conv_wgp_kernel): the input patch of a pixel region staged once in LDS
-        wtiles = 0 if (wd.bn_z or os.environ.get("YH_WGRAD_WAVE", "1") == "0") else self.L.yh_conv_wgrad_wave_tiles(C.byref(wd))
-        if wtiles > 0:
-            tks = tks + (129,)              # wave-private 128 x 128 tiles + stream-K (conv_wgs_kernel): `splits` = workgroups, one per CU;
-                                            # with a workspace its slot form (same workgroup counts: G + tiles - 1 slots of 64 KB)
-        for tk in tks:
+        for tk, sps in self._wgrad_candidates(self.L, wd, M, ntile):
             wd.tile_k = tk
-            if tk == 129:                   # an exact tiles x splits grid where it fills the chip, else 256 workgroups dealt (tile, 32 pixels) units
-                # Workgroups (= CUs: the form holds a whole CU) a weight gradient may take.  Alone on the chip 256 is fastest; in the
-                # two-stream backward the main chain runs beside it, and its short latency-bound kernels (finalize launches, small
-                # layers) wait for a CU while a weight gradient holds all of them: the YOLOv5s step is shortest when the weight
-                # gradients leave a quarter of the CUs alone (12.00 -> 11.90 ms), the YOLOv5l step — long kernels on both streams —
-                # when its big layers take the whole chip (43.36 -> 42.82 ms): layers under 60 GFLOP get 192, the others 256
-                # (profiles/r04_step_experiments.txt d).  Half of the budget is timed too: on the small layers the atomics (one
-                # partial tile per workgroup) dominate.
-                wflops = 2.0 * M * wd.N * wd.KH * wd.KW * wd.seg.C
-                gmax = int(os.environ.get("YH_WGS_G", "256" if wflops >= 60e9 else "192"))
-                sps = set()
-                for g in (gmax, gmax // 2):
-                    sps |= {g} | ({wtiles * (g // wtiles)} if wtiles <= g else set())
-                sps = sorted(sps)
-            else:
-                sps = [1024] if tk == 40 else sorted({splits_for(t, tk) for t in (256, 512, 768, 1024, 1536)})
             for sp in sps:
                 wd.splits = sp
                 if wd.partial and self.L.yh_conv_wgrad_ws_bytes(C.byref(wd)) > wd.partial_bytes:
@@ -286,18 +242,59 @@ class TunerMixin:
         return best[0]
 
     @staticmethod
+    def _wgrad_info(L, wd, tile_k=None):
+        """the library's plan for this descriptor (yh_conv_wgrad_info), optionally with another tile_k asked; no device needed"""
+        o, saved = WgradInfo(), wd.tile_k
+        if tile_k is not None:
+            wd.tile_k = tile_k
+        L.yh_conv_wgrad_info(C.byref(wd), C.byref(o))      # (the rc speaks of operands and workspace: the callers want the plan)
+        wd.tile_k = saved
+        return o
+
+    @staticmethod
+    def _wgrad_splits_for(L, wd, M, ntile, total, tk=0):
+        nt = L.yh_conv_wgrad_tiles2(wd.N, wd.KH * wd.KW * wd.seg.C, tk) if tk == 128 else ntile
+        return max(1, min((M + 255) // 256, (total + nt - 1) // nt))
+
+    @staticmethod
+    def _wgrad_candidates(L, wd, M, ntile):
+        """[(tile_k, [splits ...])] _tune_wgrad_splits times for this descriptor, in that order.  Which requests the library would
+        honour is read from its plan; which of them are worth timing is decided here.  Needs no device."""
+        honoured = lambda tk: TunerMixin._wgrad_info(L, wd, tk).tile_k == tk     # noqa: E731
+        tks = (0, 64) if honoured(64) else (0,)
+        if honoured(32):
+            tks = tks + (32, 35)            # the general tiling with 32-pixel k-steps (two blocks per CU): 8 waves of 32 x 64 / 4 of 64 x 64
+        if honoured(128) and wd.N > 32 and not wd.bn_z:
+            tks = tks + (128,)              # the general 128-column tiling on a layer that defaults to a wide one
+        if not wd.partial and TunerMixin._wgrad_info(L, wd, 40).form == YH_WGRAD_PATCH:
+            tks = tks + (40,)               # patch form (conv_wgp_kernel): the input patch of a pixel region staged once in LDS
+        wave = TunerMixin._wgrad_info(L, wd, 129)
+        wtiles = wave.tiles if wave.form == YH_WGRAD_WAVE and not wd.bn_z and os.environ.get("YH_WGRAD_WAVE", "1") != "0" else 0
+        if wtiles > 0:
+            tks = tks + (129,)              # wave-private 128 x 128 tiles + stream-K (conv_wgs_kernel): `splits` = workgroups, one per CU;
+                                            # with a workspace its slot form (same workgroup counts: G + tiles - 1 slots of 64 KB)
+        cands = []
+        for tk in tks:
+            if tk == 129:                   # an exact tiles x splits grid where it fills the chip, else 256 workgroups dealt (tile, 32 pixels) units
+                # Workgroups (= CUs: the form holds a whole CU) a weight gradient may take.  Alone on the chip 256 is fastest; in the
+                # two-stream backward the main chain runs beside it, and its short latency-bound kernels (finalize launches, small
+                # layers) wait for a CU while a weight gradient holds all of them: the YOLOv5s step is shortest when the weight
+                # gradients leave a quarter of the CUs alone (12.00 -> 11.90 ms), the YOLOv5l step — long kernels on both streams —
+                # when its big layers take the whole chip (43.36 -> 42.82 ms): layers under 60 GFLOP get 192, the others 256
+                # (profiles/r04_step_experiments.txt d).  Half of the budget is timed too: on the small layers the atomics (one
+                # partial tile per workgroup) dominate.
+                wflops = 2.0 * M * wd.N * wd.KH * wd.KW * wd.seg.C
+                gmax = int(os.environ.get("YH_WGS_G", "256" if wflops >= 60e9 else "192"))
+                sps = set()
+                for g in (gmax, gmax // 2):
+                    sps |= {g} | ({wtiles * (g // wtiles)} if wtiles <= g else set())
+                sps = sorted(sps)
+            else:
+                sps = [1024] if tk == 40 else sorted({TunerMixin._wgrad_splits_for(L, wd, M, ntile, t, tk) for t in (256, 512, 768, 1024, 1536)})
+            cands.append((tk, sps))
+        return cands
+
+    @staticmethod
     def _wgrad_name(L, wd):
-        """instantiation yh_conv_wgrad launches for this descriptor, profiler spelling (64-pixel k-steps on the wide tilings:
-        csrc/conv_wgrad.hip, yh_conv_wgrad)"""
-        name = L.yh_conv_wgrad_kernel_name2(wd.N, wd.KH * wd.KW * wd.seg.C, wd.tile_k).decode()
-        if wd.tile_k == 64:
-            name = _WGRAD_TK64.get(name, name)
-        if wd.bn_z:                        # last template argument: BatchNorm backward fused into the operand loader
-            name = name[:-len(", false>")] + ", true>"
-        if wd.tile_k == 129 and L.yh_conv_wgrad_wave_tiles(C.byref(wd)) > 0:
-            return L.yh_conv_wgrad_wave_name(C.byref(wd)).decode()
-        if wd.tile_k == 40 and L.yh_conv_wgrad_patch_ok(C.byref(wd)):
-            buf = C.create_string_buffer(64)
-            L.yh_conv_wgrad_patch_name(C.byref(wd), buf, 64)
-            name = buf.value.decode() or name
-        return name
+        """instantiation yh_conv_wgrad launches for this descriptor, profiler spelling"""
+        return TunerMixin._wgrad_info(L, wd).name.decode()
