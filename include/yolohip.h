@@ -441,7 +441,8 @@ typedef struct yh_decode_desc {
 /* Full decode to (B, sum(A*H*W), 5+nc) fp32, the tensor do_inference returns.    */
 int yh_decode_full(const yh_decode_desc* d, const void* const* preds, float* out, yh_stream stream);
 /* Fused decode + candidate filter, order preserving.
- *  cand: [B][cap][6] fp32 (xmin,ymin,xmax,ymax,conf,cls) ; ncand: [B] int32 (may exceed cap: overflow)
+ *  cand: [B][cap][6] fp32 (xmin,ymin,xmax,ymax,conf,cls) ; ncand: [B] int32, written not read: the table starts at row 0 (may
+ *  exceed cap: rows past cap are counted, not stored).  yh_decode_filter_view below appends instead.
  *  conf_ge: obj >= conf_thr ; cls_gt: cls_conf > cls_thr (v5) / obj*max>=conf & cls>=thr (yolox) */
 int yh_decode_filter(const yh_decode_desc* d, const void* const* preds, float conf_thr, float cls_thr,
                      float* cand, int32_t* ncand, int cap, void* ws, yh_stream stream);
@@ -449,6 +450,24 @@ int yh_decode_filter(const yh_decode_desc* d, const void* const* preds, float co
  *  with coalesced loads), their candidates are ordered by a second, per-image pass.  ws == NULL: one workgroup per image walks
  *  the predictions (same result; for small heads).                                                                     */
 size_t yh_decode_filter_ws_bytes(const yh_decode_desc* d);
+/* One pass of test-time augmentation (trainer/eval_yolov5.py:152-179) through the same filter, both forms.  Between the decode
+ * and the xywh -> xyxy step the centre-format box (cx, cy, w, h) is mapped back to the original image, in the evaluator's order:
+ * all four values times 1.0f / scale (the reciprocal taken once in fp32 — what torch's device kernel computes for
+ * `ripe[..., :4] /= s` with a host scalar — not a division per value), then cy = img_h - cy for flip_axis 2 or cx = img_w - cx
+ * for flip_axis 3.  Thresholds, class arg-max and the candidate rule are those of yh_decode_filter.
+ * The candidates are APPENDED: on entry ncand[b] is the number of rows image b's table holds already (zero it before the first
+ * pass; negative counts as 0); the pass stores its candidates from that row on, in prediction order, and leaves
+ * ncand[b] = old + its count.  Rows at or past cap are counted, not stored.  scale 1, flip_axis 0 and ncand == 0 give
+ * yh_decode_filter's table bit for bit.  ws as for yh_decode_filter (staging area and counts are per call), or NULL.
+ * YH_EINVAL: xf NULL, flip_axis outside {0, 2, 3}, scale not positive and finite.  Enqueues only: no allocation, no sync. */
+typedef struct yh_view_xform {
+    float   scale;
+    int32_t flip_axis;            /* 0 none, 2 rows, 3 columns */
+    float   img_h, img_w;         /* of the original image, pixels */
+} yh_view_xform;
+int yh_decode_filter_view(const yh_decode_desc* d, const void* const* preds, const yh_view_xform* xf,
+                          float conf_thr, float cls_thr, float* cand, int32_t* ncand /* in/out */, int cap,
+                          void* ws, yh_stream stream);
 /* The same filter applied to an already decoded (B, N, 5+nc) fp32 tensor — the argument of
  * YOLOV5Evaluator.numba_nms (trainer/eval_yolov5.py:261-286); used after TTA merging.  `yolox`: 0 YOLOv5 single label,
  * 1 YOLOX, 2 YOLOv5 multi-label (hyp['mutil_label'], :276-279: one candidate per (prediction, class) with cls*obj >= cls_thr,

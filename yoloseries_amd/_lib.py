@@ -103,6 +103,11 @@ class DecodeDesc(C.Structure):
     ]
 
 
+class ViewXform(C.Structure):
+    """yh_view_xform: how one test-time-augmentation pass maps back to the original image (yh_decode_filter_view)"""
+    _fields_ = [("scale", C.c_float), ("flip_axis", C.c_int32), ("img_h", C.c_float), ("img_w", C.c_float)]
+
+
 class BnFoldItem(C.Structure):
     _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("rm", C.c_void_p), ("rv", C.c_void_p),
                 ("scale", C.c_void_p), ("shift", C.c_void_p), ("eps", C.c_float), ("C", C.c_int32)]
@@ -196,6 +201,7 @@ _SIGS = {
     "yh_decode_full": (_i32, [C.POINTER(DecodeDesc), C.POINTER(_vp), _vp, _vp]),
     "yh_decode_filter": (_i32, [C.POINTER(DecodeDesc), C.POINTER(_vp), _f32, _f32, _vp, _vp, _i32, _vp, _vp]),
     "yh_decode_filter_ws_bytes": (C.c_size_t, [C.POINTER(DecodeDesc)]),
+    "yh_decode_filter_view": (_i32, [C.POINTER(DecodeDesc), C.POINTER(_vp), C.POINTER(ViewXform), _f32, _f32, _vp, _vp, _i32, _vp, _vp]),
     "yh_filter_decoded": (_i32, [_vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _i32, _vp]),
     "yh_exec_op": (_i32, [C.c_char_p, C.POINTER(_i32)]),
     "yh_exec": (_i32, [C.POINTER(Cmd), _i32, C.POINTER(_vp), _i32, C.POINTER(_i32)]),

@@ -4,11 +4,17 @@
 //   decode_filter — fused decode + confidence filter + best-class selection; candidates are
 //                   compacted per image IN PREDICTION ORDER (wave ballots + block scan), so the
 //                   whole decoded tensor never leaves the GPU (the reference copies it to the host).
+//                   yh_decode_filter_view is the same filter for one pass of test-time augmentation
+//                   (eval_yolov5.py:152-179): the decoded centre-format box is un-scaled and un-flipped
+//                   before the xywh -> xyxy step, and the candidates are APPENDED to the table.  The un-scale
+//                   is x * (1.0f / scale), the reciprocal taken once in fp32 on the host: that is what torch's
+//                   device kernel for `ripe[..., :4] /= s` (division by a host scalar) computes, not x / scale.
 //   nms_batched   — one workgroup per image: greedy arg-max NMS exactly as numba_nms does it
 //                   (first maximum on ties, class offset added in fp32 before the IoU, inclusive
 //                   threshold, NaN IoU never suppresses), early exit after max_keep picks, then
 //                   the "merge" filter of eval_yolov5.py:306-315.  Wave-level arg-max via shuffles.
 // All comparisons are in fp32 with the reference's operation order (compiled with -ffp-contract=off).
+#include <float.h>
 #include "common.h"
 
 namespace {
@@ -20,6 +26,15 @@ template <> __device__ __forceinline__ float ldv<float>(const float* p) { return
 template <> __device__ __forceinline__ float ldv<uint16_t>(const uint16_t* p) { return bf2f(*p); }
 
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// view of one pass: how its centre-format boxes map back to the original image, and whether its candidates follow the rows
+// already in the table.  {1, 0, .., .., 0} is yh_decode_filter: x * 1.0f is x, and the table starts at row 0.
+struct ViewK {
+    float inv;                // 1.0f / scale
+    int flip;                 // 0 none, 2 rows (cy = img_h - cy), 3 columns (cx = img_w - cx)
+    float img_h, img_w;
+    int append;               // first row of image b: ncand[b] on entry instead of 0
+};
 
 struct DecK {
     yh_decode_desc d;
@@ -94,8 +109,8 @@ __global__ void decode_full_kernel(const DecK k, float* __restrict__ out)
 
 // confidence filter + best class + box of ONE prediction row (eval_yolov5.py:266-285, eval_yolox.py:206-227); true = candidate
 template <typename T>
-__device__ __forceinline__ bool eval_pred(const DecK& k, const T* row, int s, int a, int y, int x, float conf_thr, float cls_thr,
-                                          float* box, float& conf, int& cls)
+__device__ __forceinline__ bool eval_pred(const DecK& k, const ViewK& v, const T* row, int s, int a, int y, int x, float conf_thr,
+                                          float cls_thr, float* box, float& conf, int& cls)
 {
     const int nc = k.d.num_class;
     const float obj = sigm(ldv<T>(row + 4));
@@ -113,6 +128,9 @@ __device__ __forceinline__ bool eval_pred(const DecK& k, const T* row, int s, in
     if (!pass) return false;
     float cb[4];
     decode_box<T>(k, row, s, a, y, x, cb);
+    cb[0] = cb[0] * v.inv; cb[1] = cb[1] * v.inv; cb[2] = cb[2] * v.inv; cb[3] = cb[3] * v.inv;     // ripe[..., :4] /= s (:171)
+    if (v.flip == 2) cb[1] = v.img_h - cb[1];                              // eval_yolov5.py:172-175
+    if (v.flip == 3) cb[0] = v.img_w - cb[0];
     box[0] = cb[0] - cb[2] / 2.f; box[1] = cb[1] - cb[3] / 2.f;           // numba_xywh2xyxy
     box[2] = cb[0] + cb[2] / 2.f; box[3] = cb[1] + cb[3] / 2.f;
     conf = best;
@@ -122,14 +140,14 @@ __device__ __forceinline__ bool eval_pred(const DecK& k, const T* row, int s, in
 // One workgroup (1024 threads) per image walks the predictions in order (kept for heads too small to fill the chip otherwise
 // and as the cross-check of the two-pass path in the tests: yh_decode_filter with ws == NULL).
 template <typename T>
-__global__ __launch_bounds__(1024) void decode_filter_kernel(const DecK k, float conf_thr, float cls_thr,
+__global__ __launch_bounds__(1024) void decode_filter_kernel(const DecK k, const ViewK v, float conf_thr, float cls_thr,
                                                              float* __restrict__ cand, int32_t* __restrict__ ncand, int cap)
 {
     __shared__ int wave_cnt[16];
     __shared__ int base_s;
     const int b = blockIdx.x;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    if (t == 0) base_s = 0;
+    if (t == 0) base_s = v.append ? max(ncand[b], 0) : 0;
     __syncthreads();
     float* out = cand + (size_t)b * cap * 6;
     for (int p0 = 0; p0 < k.ntot; p0 += 1024) {
@@ -141,7 +159,7 @@ __global__ __launch_bounds__(1024) void decode_filter_kernel(const DecK k, float
             int s, a, y, x;
             locate(k, pi, s, a, y, x);
             const T* row = cell_ptr<T>(k, b, s, a, y, x);
-            flag = eval_pred<T>(k, row, s, a, y, x, conf_thr, cls_thr, box, conf, cls);
+            flag = eval_pred<T>(k, v, row, s, a, y, x, conf_thr, cls_thr, box, conf, cls);
         }
         const unsigned long long bal = __ballot(flag);
         const int within = __popcll(bal & ((1ull << lane) - 1ull));
@@ -153,7 +171,7 @@ __global__ __launch_bounds__(1024) void decode_filter_kernel(const DecK k, float
         const int base = base_s;
         if (flag) {
             const int pos = base + before + within;
-            if (pos < cap) {
+            if ((unsigned)pos < (unsigned)cap) {                  // unsigned: a base near INT_MAX that wraps must not store either
                 float* o = out + (size_t)pos * 6;
                 o[0] = box[0]; o[1] = box[1]; o[2] = box[2]; o[3] = box[3]; o[4] = conf; o[5] = (float)cls;
             }
@@ -172,10 +190,10 @@ __global__ __launch_bounds__(1024) void decode_filter_kernel(const DecK k, float
 // loads and evaluates one (pixel, anchor) per thread, wave a = anchor a, so a wave ballot orders the candidates of the key
 // (stage, anchor, chunk) — and leaves them in a staging area [B][nkeys][64][6] with their counts; pass 2 (one block per
 // image) turns the counts into offsets in prediction order and moves the candidates to their final rows.  Same arithmetic,
-// same order as decode_filter_kernel.
+// same order as decode_filter_kernel.  Appending (ViewK::append) concerns pass 2 alone: its first row is ncand[b].
 constexpr int DPIX = 64;
 template <typename T>
-__global__ __launch_bounds__(256) void decode_scan_kernel(const DecK k, float conf_thr, float cls_thr,
+__global__ __launch_bounds__(256) void decode_scan_kernel(const DecK k, const ViewK v, float conf_thr, float cls_thr,
                                                           float* __restrict__ stage, int32_t* __restrict__ counts, int nkeys)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
@@ -234,7 +252,7 @@ __global__ __launch_bounds__(256) void decode_scan_kernel(const DecK k, float co
         const int pidx = p0 + lane;
         const int y = pidx / k.d.W[s], x = pidx - y * k.d.W[s];
         const T* row = tile + lane * lds_ld + a * (5 + k.d.num_class);
-        flag = eval_pred<T>(k, row, s, a, y, x, conf_thr, cls_thr, box, conf, cls);
+        flag = eval_pred<T>(k, v, row, s, a, y, x, conf_thr, cls_thr, box, conf, cls);
     }
     const unsigned long long bal = __ballot(flag);
     const int key = k.kstart[s] + a * nchunk + c;
@@ -246,13 +264,13 @@ __global__ __launch_bounds__(256) void decode_scan_kernel(const DecK k, float co
 }
 
 __global__ __launch_bounds__(1024) void decode_gather_kernel(const float* __restrict__ stage, const int32_t* __restrict__ counts, int nkeys,
-                                                              float* __restrict__ cand, int32_t* __restrict__ ncand, int cap)
+                                                              float* __restrict__ cand, int32_t* __restrict__ ncand, int cap, int append)
 {
     __shared__ int wsum[16];
     __shared__ int base_s;
     const int b = blockIdx.x;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    if (t == 0) base_s = 0;
+    if (t == 0) base_s = append ? max(ncand[b], 0) : 0;
     __syncthreads();
     float* out = cand + (size_t)b * cap * 6;
     for (int k0 = 0; k0 < nkeys; k0 += 1024) {
@@ -269,7 +287,7 @@ __global__ __launch_bounds__(1024) void decode_gather_kernel(const float* __rest
         const int base = base_s;
         int pos = base + before + incl - cnt;
         const float* src = stage + ((size_t)b * nkeys + key) * DPIX * 6;
-        for (int i = 0; i < cnt && pos < cap; ++i, ++pos) {
+        for (int i = 0; i < cnt && (unsigned)pos < (unsigned)cap; ++i, ++pos) {      // unsigned: as in decode_filter_kernel
 #pragma unroll
             for (int e = 0; e < 6; ++e) out[(size_t)pos * 6 + e] = src[i * 6 + e];
         }
@@ -632,41 +650,63 @@ extern "C" size_t yh_decode_filter_ws_bytes(const yh_decode_desc* d)
     return (size_t)d->B * nkeys * (DPIX * 6 * 4 + 4);
 }
 
-extern "C" int yh_decode_filter(const yh_decode_desc* d, const void* const* preds, float conf_thr, float cls_thr,
-                                float* cand, int32_t* ncand, int cap, void* ws, yh_stream stream)
+namespace {
+int decode_filter_launch(const yh_decode_desc* d, const void* const* preds, const ViewK& v, float conf_thr, float cls_thr,
+                         float* cand, int32_t* ncand, int cap, void* ws, yh_stream stream, const char* who)
 {
     DecK k;
-    int rc = fill_deck(d, preds, &k, "yh_decode_filter");
+    int rc = fill_deck(d, preds, &k, who);
     if (rc) return rc;
-    YH_CHECK_ARG(cand && ncand && cap > 0 && cap % 4 == 0, "yh_decode_filter: cand/ncand null or cap not a multiple of 4");
+    YH_CHECK_ARG(cand && ncand && cap > 0 && cap % 4 == 0, "%s: cand/ncand null or cap not a multiple of 4", who);
     if (ws) {
-        YH_CHECK_ARG(yh_aligned16(ws) && d->num_anchor <= 4, "yh_decode_filter: workspace unaligned");
+        YH_CHECK_ARG(yh_aligned16(ws) && d->num_anchor <= 4, "%s: workspace unaligned", who);
         const int nkeys = k.kstart[MAXS], nchunks = k.cstart[MAXS];
         float* stage = reinterpret_cast<float*>(ws);
         int32_t* counts = reinterpret_cast<int32_t*>(stage + (size_t)d->B * nkeys * DPIX * 6);
         int ldmax = 0;
         for (int s = 0; s < d->num_stage; ++s) ldmax = d->ldp[s] > ldmax ? d->ldp[s] : ldmax;
         const size_t sm = (size_t)DPIX * ((size_t)ldmax * (d->pred_is_f32 ? 4 : 2) + 16);      // rows padded by 16 bytes (bank conflicts)
-        YH_CHECK_ARG(sm <= 160 * 1024, "yh_decode_filter: prediction rows of %d elements do not fit the LDS tile", ldmax);
+        YH_CHECK_ARG(sm <= 160 * 1024, "%s: prediction rows of %d elements do not fit the LDS tile", who, ldmax);
         const dim3 grid(nchunks, d->B);
+        char label[64];
         if (d->pred_is_f32) {
             static YhDevOnce attr;
             if (attr.need()) { attr.set((const void*)decode_scan_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr.done(); }
-            hipLaunchKernelGGL((decode_scan_kernel<float>), grid, dim3(256), sm, (hipStream_t)stream, k, conf_thr, cls_thr, stage, counts, nkeys);
+            hipLaunchKernelGGL((decode_scan_kernel<float>), grid, dim3(256), sm, (hipStream_t)stream, k, v, conf_thr, cls_thr, stage, counts, nkeys);
         } else {
             static YhDevOnce attr;
             if (attr.need()) { attr.set((const void*)decode_scan_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr.done(); }
-            hipLaunchKernelGGL((decode_scan_kernel<uint16_t>), grid, dim3(256), sm, (hipStream_t)stream, k, conf_thr, cls_thr, stage, counts, nkeys);
+            hipLaunchKernelGGL((decode_scan_kernel<uint16_t>), grid, dim3(256), sm, (hipStream_t)stream, k, v, conf_thr, cls_thr, stage, counts, nkeys);
         }
-        YH_CHECK_LAUNCH("yh_decode_filter(scan)");
-        hipLaunchKernelGGL(decode_gather_kernel, dim3(d->B), dim3(1024), 0, (hipStream_t)stream, stage, counts, nkeys, cand, ncand, cap);
-        YH_CHECK_LAUNCH("yh_decode_filter(gather)");
+        snprintf(label, sizeof(label), "%s(scan)", who);
+        YH_CHECK_LAUNCH(label);
+        hipLaunchKernelGGL(decode_gather_kernel, dim3(d->B), dim3(1024), 0, (hipStream_t)stream, stage, counts, nkeys, cand, ncand, cap, v.append);
+        snprintf(label, sizeof(label), "%s(gather)", who);
+        YH_CHECK_LAUNCH(label);
         return YH_OK;
     }
-    if (d->pred_is_f32) hipLaunchKernelGGL((decode_filter_kernel<float>), dim3(d->B), dim3(1024), 0, (hipStream_t)stream, k, conf_thr, cls_thr, cand, ncand, cap);
-    else                hipLaunchKernelGGL((decode_filter_kernel<uint16_t>), dim3(d->B), dim3(1024), 0, (hipStream_t)stream, k, conf_thr, cls_thr, cand, ncand, cap);
-    YH_CHECK_LAUNCH("yh_decode_filter");
+    if (d->pred_is_f32) hipLaunchKernelGGL((decode_filter_kernel<float>), dim3(d->B), dim3(1024), 0, (hipStream_t)stream, k, v, conf_thr, cls_thr, cand, ncand, cap);
+    else                hipLaunchKernelGGL((decode_filter_kernel<uint16_t>), dim3(d->B), dim3(1024), 0, (hipStream_t)stream, k, v, conf_thr, cls_thr, cand, ncand, cap);
+    YH_CHECK_LAUNCH(who);
     return YH_OK;
+}
+}  // namespace
+
+extern "C" int yh_decode_filter(const yh_decode_desc* d, const void* const* preds, float conf_thr, float cls_thr,
+                                float* cand, int32_t* ncand, int cap, void* ws, yh_stream stream)
+{
+    const ViewK v = {1.0f, 0, 0.f, 0.f, 0};
+    return decode_filter_launch(d, preds, v, conf_thr, cls_thr, cand, ncand, cap, ws, stream, "yh_decode_filter");
+}
+
+extern "C" int yh_decode_filter_view(const yh_decode_desc* d, const void* const* preds, const yh_view_xform* xf,
+                                     float conf_thr, float cls_thr, float* cand, int32_t* ncand, int cap, void* ws, yh_stream stream)
+{
+    YH_CHECK_ARG(xf != nullptr, "yh_decode_filter_view: null view transform");
+    YH_CHECK_ARG(xf->flip_axis == 0 || xf->flip_axis == 2 || xf->flip_axis == 3, "yh_decode_filter_view: flip_axis %d is not 0, 2 or 3", xf->flip_axis);
+    YH_CHECK_ARG(xf->scale > 0.f && xf->scale <= FLT_MAX, "yh_decode_filter_view: scale must be positive and finite");
+    const ViewK v = {1.0f / xf->scale, xf->flip_axis, xf->img_h, xf->img_w, 1};
+    return decode_filter_launch(d, preds, v, conf_thr, cls_thr, cand, ncand, cap, ws, stream, "yh_decode_filter_view");
 }
 
 extern "C" int yh_filter_decoded(const float* dec, int B, int N, int num_class, float conf_thr, float cls_thr, int yolox,

@@ -2,7 +2,9 @@
 
 forward -> decode -> candidate filter -> class-aware greedy NMS -> merge filter all run on
 the GPU; only the final (n,6) rows per image cross PCIe (the reference copies the whole
-decoded (B, 25200, 85) tensor to the host, :265).
+decoded (B, 25200, 85) tensor to the host, :265).  With use_tta each of the three passes is
+decoded and filtered straight from its head tensors into one candidate table
+(_tta_from_heads): no decoded tensor, no concatenation.
 """
 import ctypes as C
 
@@ -11,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import _lib
-from .._lib import DecodeDesc, check, lib
+from .._lib import DecodeDesc, ViewXform, check, lib
 from ..layout import to_cell_major
 
 __all__ = ['YOLOV5Evaluator']
@@ -49,11 +51,15 @@ class YOLOV5Evaluator:
     @torch.no_grad()
     def __call__(self, inputs):
         """:param inputs: (b, 3, h, w) -> list (len b) of FloatTensor (n, 6) [xmin, ymin, xmax, ymax, conf, cls] on CPU, or None"""
-        if self.use_tta:
+        if self.use_tta and self.hyp.get('mutil_label', False):       # through the decoded tensor, like _nms_from_heads
             merge_preds_out, _ = self.test_time_augmentation(inputs)
             if self.hyp.get("wfb", False):
                 raise NotImplementedError("weighted box fusion is outside the HIP hot path (wfb: false in every shipped config)")
             outs = self.numba_nms(merge_preds_out)
+        elif self.use_tta:
+            if self.hyp.get("wfb", False):
+                raise NotImplementedError("weighted box fusion is outside the HIP hot path (wfb: false in every shipped config)")
+            outs = self._tta_from_heads(inputs)
         else:
             stage_preds = self.yolo(inputs)
             outs = self._nms_from_heads(stage_preds)
@@ -128,6 +134,45 @@ class YOLOV5Evaluator:
             if cap >= n or int(ncand.max().item()) <= cap:
                 break
             cap = ((n + 3) // 4) * 4
+        return self._run_nms(cand, ncand, B, cap)
+
+    _TTA_PASSES = ((1, None), (0.83, 2), (0.67, 3))       # (scale, flipped axis) of test_time_augmentation (:159-160)
+    _TTA_FIRST_CAP = 3 * 16384                            # rows per image of the first try: _nms_from_heads' figure per pass
+
+    def _view_desc(self, stage_preds, img):
+        """descriptor of the heads one TTA pass returned for the network input `img`; `img` is unused here — the YOLOX override
+        takes its strides from it"""
+        return self._desc(stage_preds)
+
+    @torch.no_grad()
+    def _tta_from_heads(self, inputs):
+        """test_time_augmentation + numba_nms without the decoded tensors: each pass is decoded, filtered, un-scaled and
+        un-flipped straight from its heads (yh_decode_filter_view) and appended to one candidate table, in the order of the
+        concatenation, before the next forward overwrites the engine's head buffers; one NMS over the table.  Same rows as
+        numba_nms(test_time_augmentation(inputs)[0]), bit for bit."""
+        img_h, img_w = inputs.size(2), inputs.size(3)
+        cap = None
+        while True:
+            cand, n_all = None, 0
+            for s, f in self._TTA_PASSES:
+                img = inputs.flip(dims=(f,)) if f else inputs
+                img = self.scale_img(img, s)
+                d, canon, ptrs = self._view_desc(self.yolo(img), img)
+                n = sum(d.num_anchor * d.H[i] * d.W[i] for i in range(d.num_stage))
+                n_all += n
+                if cand is None:
+                    dev, B = canon[0].device, d.B
+                    if cap is None:
+                        cap = min(((3 * n + 3) // 4) * 4, self._TTA_FIRST_CAP)
+                    cand = torch.empty(B, cap, 6, dtype=torch.float32, device=dev)
+                    ncand = torch.zeros(B, dtype=torch.int32, device=dev)
+                xf = ViewXform(s, f or 0, img_h, img_w)
+                check(lib().yh_decode_filter_view(C.byref(d), ptrs, C.byref(xf), float(self.conf_threshold), float(self.cls_threshold),
+                                                  cand.data_ptr(), ncand.data_ptr(), cap, _decode_ws(self, d, dev), _lib.stream_ptr()),
+                      "yh_decode_filter_view")
+            if cap >= n_all or int(ncand.max().item()) <= cap:
+                break
+            cap = ((n_all + 3) // 4) * 4                  # one row per prediction of the three passes: cannot overflow
         return self._run_nms(cand, ncand, B, cap)
 
     _FILTER_MODES = (0, 2)        # yh_filter_decoded mode of the single-label / hyp['mutil_label'] candidate rule (:266-286)

@@ -61,6 +61,12 @@ class YOLOXEvaluator(YOLOV5Evaluator):
         for s in range(d.num_stage):
             d.stride[s] = float(img_h) / float(d.H[s])        # input_img_h / fm_h (eval_yolox.py:142-144)
 
+    def _view_desc(self, stage_preds, img):
+        """strides from the height of the pass's network input, as do_inference sets them"""
+        d, canon, ptrs = self._desc(self._stage_list(stage_preds))
+        self._set_strides(d, img.size(2))
+        return d, canon, ptrs
+
     @torch.no_grad()
     def do_inference(self, inputs):
         stage_preds = self.yolo(inputs)
@@ -79,9 +85,11 @@ class YOLOXEvaluator(YOLOV5Evaluator):
 
     @torch.no_grad()
     def __call__(self, inputs):
-        if self.use_tta:
+        if self.use_tta and self.hyp.get('mutil_label', False):       # through the decoded tensor, like _nms_from_heads
             merge_preds_out, _ = self.test_time_augmentation(inputs)
             outs = self.numba_nms(merge_preds_out)
+        elif self.use_tta:
+            outs = self._tta_from_heads(inputs)                       # inherited; strides per pass from _view_desc
         else:
             outs = self._nms_from_heads(self.yolo(inputs), inputs.size(2))
         return [torch.from_numpy(x) if x is not None else None for x in outs]
