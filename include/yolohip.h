@@ -316,6 +316,17 @@ int yh_upsample2_bwd(const yh_bf16* ghi, int ldh, int B, int Hlo, int Wlo, int C
  * models/normal/yolov5s.py:16 becomes a 3x3/s1/p1 conv on this tensor.          */
 int yh_input_s2d(const float* x, int B, int Cin, int H, int W, yh_bf16* out, yh_stream stream);
 int yh_fill_u32(void* p, uint32_t v, int64_t n_words, yh_stream stream);
+/* letterbox + normalisation of a batch of raw images (utils/data_aug.py:21-70 letter_resize_img and
+ * dataset/data_collater.py normal_normalization of the reference, per image on the host there):
+ *   out[b][c][y][x] = (float)v / 255.0f,  v = raw[img_off[b] + (rows[b][y] * src_w + cols[b][x]) * 3 + c],
+ *   or v = fill_value where rows[b][y] or cols[b][x] is -1 (the letterbox border).
+ * raw: the images HWC uint8, concatenated without padding (image b starts at byte img_off[b], any alignment);
+ * src_hw[b] = {src_h, src_w}; rows [B][H] / cols [B][W] hold the source row / column of every output row / column.
+ * The caller owns the validity of the tables (every entry -1 or inside its image).  W % 4 == 0, out and cols 16-byte
+ * aligned, 0 <= fill_value <= 255.                                                                                  */
+int yh_letterbox_batch(const uint8_t* raw, const int64_t* img_off, const int32_t* src_hw,
+                       const int32_t* rows, const int32_t* cols,
+                       int B, int H, int W, int fill_value, float* out /* (B,3,H,W) */, yh_stream stream);
 
 /* ------------------------------------------------------------------------ *
  * Parameter arena: gather/scatter between the fp32 master parameters and the

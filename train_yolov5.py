@@ -58,16 +58,19 @@ class SyntheticLoader:
 
 class PrefetchedDataset:
     """the reference's data path on a synthetic dataset: torch DataLoader -> fixed_imgsize_collate_fn
-    (dataset/data_collater.py:20-64) -> DataPrefetcher (dataset/data_prefetcher.py:6-56, train_yolov5.py:458-497)"""
+    (dataset/data_collater.py:20-64) -> DataPrefetcher (dataset/data_prefetcher.py:6-56, train_yolov5.py:458-497).
+    device_letterbox=True: the workers ship the uint8 images (raw_imgsize_collate_fn) and DeviceLetterboxPrefetcher letterboxes
+    and normalises them on the GPU; the batches are the same bit for bit."""
 
-    def __init__(self, steps, batch, img, num_class, seed, workers=0):
+    def __init__(self, steps, batch, img, num_class, seed, workers=0, device_letterbox=False):
         from functools import partial
         from torch.utils.data import DataLoader
-        from yoloseries_amd.dataset import DataPrefetcher, SyntheticDetectionDataset, fixed_imgsize_collate_fn
-        self._prefetcher = DataPrefetcher
+        from yoloseries_amd.dataset import (DataPrefetcher, DeviceLetterboxPrefetcher, SyntheticDetectionDataset, fixed_imgsize_collate_fn,
+                                            raw_imgsize_collate_fn)
+        self._prefetcher = DeviceLetterboxPrefetcher if device_letterbox else DataPrefetcher
         ds = SyntheticDetectionDataset(steps * batch, img_hw=(int(img * 0.75) // 8 * 8, img), num_class=num_class, seed=seed)
         self.loader = DataLoader(ds, batch_size=batch, shuffle=False, num_workers=workers, drop_last=True, pin_memory=True,
-                                 collate_fn=partial(fixed_imgsize_collate_fn, dst_size=[img, img]))
+                                 collate_fn=partial(raw_imgsize_collate_fn if device_letterbox else fixed_imgsize_collate_fn, dst_size=[img, img]))
 
     def __len__(self):
         return len(self.loader)
@@ -111,9 +114,11 @@ class Training:
         torch.manual_seed(hyp['random_seed'])
         img = hyp['input_img_size'][0]
         if hyp.get('data_source', 'tensor') == 'dataset':
+            dlb = bool(hyp.get('device_letterbox', False))
             self.train_dataloader = PrefetchedDataset(hyp['steps_per_epoch'], hyp['batch_size'], img, hyp['num_class'], 1 + self.rank,
-                                                      hyp.get('num_workers', 0))
-            self.val_dataloader = PrefetchedDataset(hyp['val_batches'], hyp['batch_size'], img, hyp['num_class'], 101 + self.rank)
+                                                      hyp.get('num_workers', 0), device_letterbox=dlb)
+            self.val_dataloader = PrefetchedDataset(hyp['val_batches'], hyp['batch_size'], img, hyp['num_class'], 101 + self.rank,
+                                                    device_letterbox=dlb)
         else:
             shapes = hyp.get('data_source', 'tensor') == 'shapes'
             self.train_dataloader = SyntheticLoader(hyp['steps_per_epoch'], hyp['batch_size'], img, hyp['num_class'], self.device, 1 + self.rank, shapes)
@@ -281,6 +286,8 @@ def main(argv=None, training_cls=None, default_cfg=None):
                     "task (coloured rectangles, colour = class) that shows mAP rising")
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible weight gradients (yoloseries_amd.set_deterministic): "
                     "two runs on the same seed and data write the same checkpoint")
+    ap.add_argument("--device-letterbox", action="store_true", help="with --data dataset: the loader's workers ship the raw uint8 images "
+                    "and one HIP kernel letterboxes and normalises the batch on the GPU (same batches, bit for bit)")
     args = ap.parse_args(argv)
     if args.deterministic:                                               # before any model / program is built
         import yoloseries_amd
@@ -295,6 +302,11 @@ def main(argv=None, training_cls=None, default_cfg=None):
     if args.steps_per_epoch: hyp['steps_per_epoch'] = args.steps_per_epoch  # noqa: E701
     if args.model_type: hyp['model_type'] = args.model_type              # noqa: E701
     if args.data: hyp['data_source'] = args.data                         # noqa: E701
+    if args.device_letterbox:
+        if hyp.get('data_source', 'tensor') != 'dataset':
+            ap.error(f"--device-letterbox needs --data dataset: --data {hyp.get('data_source', 'tensor')} generates batches that already "
+                     "have the network's size, so there are no images to letterbox")
+        hyp['device_letterbox'] = True
     if training_cls is not None:                                         # train_yolox.py:808: Training(hyp)
         t = training_cls(hyp)
     else:

@@ -6,7 +6,8 @@
     frame with the batch's `resize_info` (preds_postprocess / gt_bbox_postprocess, :140-258) and reports
     mAP@[.5:.95], mAP@.5, mean precision / recall with `mAP_v2` (:388-390).
   * weights come from a checkpoint written by train_yolov5.py (same keys as the reference's, :202-240) or stay random.
-  * data: the synthetic dataset through DataLoader -> fixed_imgsize_collate_fn -> DataPrefetcher.
+  * data: the synthetic dataset through DataLoader -> fixed_imgsize_collate_fn -> DataPrefetcher (--device-letterbox: the
+    letterbox runs on the GPU, raw_imgsize_collate_fn -> DeviceLetterboxPrefetcher).
   Out of scope (SURVEY §8 "OUT OF SCOPE"): image dumps / plots, the auxiliary classifier, pickled box caches.
 
     python val_yolov5.py --img 640 --batch 16 --val-batches 4 [--ckpt checkpoints/yolov5_small_epoch_1.pth]
@@ -55,7 +56,7 @@ class Training:
         hyp['input_img_size'] = [int(np.ceil(s / 32) * 32) for s in hyp['input_img_size']]
         img = hyp['input_img_size'][0]
         self.val_dataloader = PrefetchedDataset(hyp['val_batches'], hyp['batch_size'], img, hyp['num_class'], 101 + self.rank,
-                                                hyp.get('num_workers', 0))
+                                                hyp.get('num_workers', 0), device_letterbox=bool(hyp.get('device_letterbox', False)))
         self.model = self.select_model().to(self.device)
         self.ema_model = ExponentialMovingAverageModel(self.model) if hyp.get('do_ema', True) else None
         self.loaded_ema = False
@@ -146,6 +147,8 @@ def main(argv=None, training_cls=None, default_cfg=None):
     ap.add_argument("--val-batches", type=int)
     ap.add_argument("--model-type")
     ap.add_argument("--ckpt")
+    ap.add_argument("--device-letterbox", action="store_true", help="letterbox and normalise the loader's uint8 images on the GPU "
+                    "(raw_imgsize_collate_fn + DeviceLetterboxPrefetcher; same batches, bit for bit)")
     args = ap.parse_args(argv)
     hyp = Config().get_config(args.cfg)
     if args.img: hyp['input_img_size'] = [args.img, args.img]            # noqa: E701
@@ -153,6 +156,7 @@ def main(argv=None, training_cls=None, default_cfg=None):
     if args.val_batches: hyp['val_batches'] = args.val_batches           # noqa: E701
     if args.model_type: hyp['model_type'] = args.model_type              # noqa: E701
     if args.ckpt: hyp['pretrained_model_path'] = args.ckpt               # noqa: E701
+    if args.device_letterbox: hyp['device_letterbox'] = True             # noqa: E701
     if training_cls is not None:
         v = training_cls(hyp)
     else:

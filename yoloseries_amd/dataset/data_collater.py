@@ -10,9 +10,10 @@ dataset/data_collater.py:16-82 produces it:
 import numpy as np
 import torch
 
-from ..utils.letterbox import letter_resize_bbox, letter_resize_img
+from ..utils.letterbox import letter_resize_bbox, letter_resize_img, pack_raw_batch
 
-__all__ = ['fixed_imgsize_collate_fn', 'test_dataset_collate_fn', 'normal_normalization']
+__all__ = ['fixed_imgsize_collate_fn', 'test_dataset_collate_fn', 'normal_normalization', 'raw_imgsize_collate_fn',
+           'raw_test_collate_fn']
 
 
 def normal_normalization(img):
@@ -45,13 +46,43 @@ def fixed_imgsize_collate_fn(data_in, dst_size):
         infos.append(info)
         rows.append(_annotation_rows(ann, info, index))
         ids.append(img_id)
-    ann_out = torch.full((len(data_in), max(len(r) for r in rows), 6), -1.0)      # -1 rows = padding
+    return {'img': batch, 'ann': _padded_annotations(rows), 'resize_info': infos, 'img_id': ids}
+
+
+def _padded_annotations(rows):
+    """per-image (n, 6) rows -> (B, maxbox, 6)"""
+    ann_out = torch.full((len(rows), max(len(r) for r in rows), 6), -1.0)      # -1 rows = padding
     for index, r in enumerate(rows):
         ann_out[index, :len(r)] = r
-    return {'img': batch, 'ann': ann_out, 'resize_info': infos, 'img_id': ids}
+    return ann_out
+
+
+def _raw_batch(images, dst_size):
+    raw, img_off, src_hw, rows, cols, infos = pack_raw_batch(images, dst_size)
+    return {'raw': torch.from_numpy(raw), 'img_off': torch.from_numpy(img_off), 'src_hw': torch.from_numpy(src_hw),
+            'rows': torch.from_numpy(rows), 'cols': torch.from_numpy(cols)}, infos
+
+
+def raw_imgsize_collate_fn(data_in, dst_size):
+    """fixed_imgsize_collate_fn for the device letterbox (DeviceLetterboxPrefetcher): the same items in, but the images leave
+    the worker as they are, uint8 and concatenated ('raw', 'img_off', 'src_hw'), with the letterbox as index tables ('rows', 'cols':
+    utils/letterbox.py letterbox_tables); 'ann', 'resize_info' and 'img_id' are those of fixed_imgsize_collate_fn."""
+    first = data_in[0][0]
+    assert first.ndim == 3 and first.shape[-1] == 3, f"data's formate should be (h, w, 3), but got {first.shape}"
+    batch, infos = _raw_batch([item[0] for item in data_in], dst_size)
+    rows = [_annotation_rows(ann, info, index) for index, ((_, ann, _), info) in enumerate(zip(data_in, infos))]
+    batch.update(ann=_padded_annotations(rows), resize_info=infos, img_id=[item[2] for item in data_in])
+    return batch
 
 
 def test_dataset_collate_fn(data_in):
     """items: (already letterboxed (3,h,w) tensor, letterbox record)"""
     img = torch.stack([item[0].to(torch.float32) for item in data_in])
     return {'img': img, 'resize_info': [item[1] for item in data_in]}
+
+
+def raw_test_collate_fn(data_in, dst_size):
+    """items: (h, w, 3) uint8 images as the dataset holds them -> the raw batch of raw_imgsize_collate_fn without annotations"""
+    batch, infos = _raw_batch(list(data_in), dst_size)
+    batch['resize_info'] = infos
+    return batch

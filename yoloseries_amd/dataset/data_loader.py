@@ -12,8 +12,8 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
-from .data_collater import fixed_imgsize_collate_fn, test_dataset_collate_fn
-from .data_prefetcher import DataPrefetcher, TestDataPrefetcher
+from .data_collater import fixed_imgsize_collate_fn, raw_imgsize_collate_fn, raw_test_collate_fn, test_dataset_collate_fn
+from .data_prefetcher import DataPrefetcher, DeviceLetterboxPrefetcher, DeviceLetterboxTestPrefetcher, TestDataPrefetcher
 from .synthetic import SyntheticDetectionDataset
 
 __all__ = ["build_dataloader", "build_val_dataloader", "build_test_dataloader"]
@@ -35,16 +35,18 @@ def _seed_worker(worker_id):
 
 
 def build_dataloader(img_dir, lab_dir, name_path, input_dim, aug_hyp, cache_num, enable_data_aug,
-                     seed, batch_size, num_workers, pin_memory, shuffle, drop_last):
-    """training loader: DataLoader -> fixed_imgsize_collate_fn(dst_size=input_dim) -> DataPrefetcher on a GPU box"""
+                     seed, batch_size, num_workers, pin_memory, shuffle, drop_last, device_letterbox=False):
+    """training loader: DataLoader -> fixed_imgsize_collate_fn(dst_size=input_dim) -> DataPrefetcher on a GPU box.
+    device_letterbox=True: the workers ship the uint8 images (raw_imgsize_collate_fn) and DeviceLetterboxPrefetcher letterboxes and
+    normalises them on the GPU; `prefetcher.next()` returns the same batches, bit for bit."""
     if enable_data_aug:
         raise NotImplementedError("data augmentation (utils/data_aug.py Transforms / mosaic) is outside the hot-path scope")
     dataset = _dataset_from(img_dir, input_dim, seed)
     gen = torch.Generator().manual_seed(seed if seed else 7)
     loader = DataLoader(dataset, batch_size=batch_size, shuffle=bool(shuffle), drop_last=bool(drop_last), num_workers=num_workers,
                         pin_memory=bool(pin_memory), generator=gen, worker_init_fn=_seed_worker,
-                        collate_fn=partial(fixed_imgsize_collate_fn, dst_size=input_dim))
-    prefetcher = DataPrefetcher(loader) if torch.cuda.is_available() else None
+                        collate_fn=partial(raw_imgsize_collate_fn if device_letterbox else fixed_imgsize_collate_fn, dst_size=input_dim))
+    prefetcher = (DeviceLetterboxPrefetcher if device_letterbox else DataPrefetcher)(loader) if torch.cuda.is_available() else None
     return dataset, loader, prefetcher
 
 
@@ -68,11 +70,28 @@ class _ImagesOnly:
         return torch.from_numpy(np.ascontiguousarray(out.transpose(2, 0, 1))).float() / 255.0, info
 
 
-def build_test_dataloader(img_dir, input_dim, batch_size=1, num_workers=0):
-    """inference loader: images only, test_dataset_collate_fn, TestDataPrefetcher on a GPU box"""
+class _RawImagesOnly:
+    """test-time view of a detection dataset for the device letterbox: the (h, w, 3) uint8 image as the dataset holds it"""
+
+    def __init__(self, ds):
+        self.ds = ds
+
+    def __len__(self):
+        return len(self.ds)
+
+    def __getitem__(self, i):
+        return self.ds[i][0]
+
+
+def build_test_dataloader(img_dir, input_dim, batch_size=1, num_workers=0, device_letterbox=False):
+    """inference loader: images only, test_dataset_collate_fn, TestDataPrefetcher on a GPU box (device_letterbox=True:
+    raw_test_collate_fn and DeviceLetterboxTestPrefetcher, the same batches letterboxed on the GPU)"""
     base = _dataset_from(img_dir, input_dim, 7, length=64)
-    dataset = _ImagesOnly(base, input_dim)
+    if device_letterbox:
+        dataset, collate, prefetch = _RawImagesOnly(base), partial(raw_test_collate_fn, dst_size=input_dim), DeviceLetterboxTestPrefetcher
+    else:
+        dataset, collate, prefetch = _ImagesOnly(base, input_dim), test_dataset_collate_fn, TestDataPrefetcher
     loader = DataLoader(dataset, batch_size=batch_size, shuffle=False, drop_last=False, num_workers=num_workers, pin_memory=True,
-                        worker_init_fn=_seed_worker, collate_fn=test_dataset_collate_fn)
-    prefetcher = TestDataPrefetcher(loader) if torch.cuda.is_available() else None
+                        worker_init_fn=_seed_worker, collate_fn=collate)
+    prefetcher = prefetch(loader) if torch.cuda.is_available() else None
     return dataset, loader, prefetcher

@@ -230,6 +230,20 @@ def input_s2d(x, out):
     check(lib().yh_input_s2d(_p(x), B, Cin, H, W, _p(out), _st()), "yh_input_s2d")
 
 
+def letterbox_batch(raw, img_off, src_hw, rows, cols, out, fill_value=128):
+    """raw uint8 images (concatenated HWC) + index tables (utils/letterbox.py pack_raw_batch) -> out (B, 3, H, W) float32, on the
+    current stream.  The tables' contents are the caller's: the kernel reads raw wherever they point."""
+    B, _, H, W = out.shape
+    want = ((raw, torch.uint8, None), (img_off, torch.int64, (B,)), (src_hw, torch.int32, (B, 2)), (rows, torch.int32, (B, H)),
+            (cols, torch.int32, (B, W)), (out, torch.float32, (B, 3, H, W)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or not t.is_cuda or t.device != out.device or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"letterbox_batch: expected a contiguous {dtype} tensor of shape {shape or '(n,)'} on {out.device}, "
+                             f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+    check(lib().yh_letterbox_batch(_p(raw), _p(img_off), _p(src_hw), _p(rows), _p(cols), B, H, W, int(fill_value), _p(out), _st()),
+          "yh_letterbox_batch")
+
+
 def fill_zero(t):
     nbytes = t.numel() * t.element_size()
     assert nbytes % 4 == 0
