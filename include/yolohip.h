@@ -327,6 +327,19 @@ int yh_fill_u32(void* p, uint32_t v, int64_t n_words, yh_stream stream);
 int yh_letterbox_batch(const uint8_t* raw, const int64_t* img_off, const int32_t* src_hw,
                        const int32_t* rows, const int32_t* cols,
                        int B, int H, int W, int fill_value, float* out /* (B,3,H,W) */, yh_stream stream);
+/* bilinear resize of a batch, the arithmetic of torch's F.interpolate(mode='bilinear', align_corners=False) on the CPU bit for bit
+ * (the multi-scale training of the reference, train_yolov5.py:526-544): per axis scale = float(n_in) / float(n_out),
+ * src = max(fma(scale, d + 0.5, -0.5), 0), i0 = min(int(src), n_in-1), i1 = min(i0+1, n_in-1), l1 = src - i0, l0 = 1 - l1;
+ * out = fma(a0, fma(A, b0, B*b1), a1 * fma(C, b0, D*b1)), a / b the row / column weights, A B | C D the taps of rows y0 | y1;
+ * where Ho + Wo <= 128 torch runs another kernel, and so does this: out = fma(a1*b1, D, fma(a1*b0, C, fma(a0*b0, A, (a0*b1)*B))).
+ * (torch's general kernel is itself not unique in the last place: with another thread count its own result can differ; the
+ * form above is what it computes with its default threads on large batches, recorded in tests/golden/g16_multiscale.npz)
+ * x (B,C,H,W) fp32 -> out (B,C,Ho,Wo) fp32, any sizes; out 16-byte aligned.                                                   */
+int yh_resize_bilinear(const float* x, int B, int C, int H, int W, int Ho, int Wo, float* out, yh_stream stream);
+/* the same samples written as the stem's input: x (B,Cin<=4,H,W) fp32 -> out (B,Ho/2,Wo/2,16) bf16 in yh_input_s2d's channel
+ * order, zero padding and fp32 -> bf16 conversion; equal to yh_input_s2d(yh_resize_bilinear(x)) bit for bit with no fp32
+ * intermediate in memory.  Ho and Wo even; out 16-byte aligned.                                                               */
+int yh_resize_bilinear_s2d(const float* x, int B, int Cin, int H, int W, int Ho, int Wo, yh_bf16* out, yh_stream stream);
 
 /* ------------------------------------------------------------------------ *
  * Parameter arena: gather/scatter between the fp32 master parameters and the

@@ -8,6 +8,14 @@ loader's iterator (worker start-up included: with 8 workers a later start of the
 queued before it) to the synchronize after its last batch.
 
     python tools/bench_ingest.py [--src 480 640] [--img 640] [--batch 64] [--workers 0 8] [--reps 5] [--out profiles/ingest_letterbox.json]
+
+--multiscale measures the multi-scale ingest instead (utils/multiscale.py): a (batch, 3, img, img) fp32 batch resized to each of
+--sizes and written as the stem's bf16 space-to-depth input, three ways -- (a) F.interpolate on the device + yh_input_s2d, the only
+route before the resize kernels, (b) yh_resize_bilinear + yh_input_s2d, (c) yh_resize_bilinear_s2d -- alternating, medians of --reps
+runs of 20 launches after 5 warm-ups, with the bytes each route has to move and the share of the 8 TB/s HBM peak that this amounts to;
+and what a miss of the program cache costs: the first training step of YOLOv5s at a shape it has not seen, against a later one.
+
+    python tools/bench_ingest.py --multiscale [--img 640] [--batch 64] [--sizes 320 608 960] [--out profiles/ingest_multiscale.json]
 """
 import argparse
 import json
@@ -68,8 +76,88 @@ def kernel_rate(src_hw, img, batch, reps):
             "border_only_output_TB_per_s": nbytes / statistics.median(ms["border_only"]) / 1e9}
 
 
+HBM_PEAK_B_PER_S = 8e12             # MI355X specification; about 6.3e12 is achievable by a streaming kernel
+
+
+def _timed(fn, launches=20, warmup=5):
+    for _ in range(warmup):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(launches):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / launches
+
+
+def multiscale_rates(img, batch, sizes, reps):
+    import torch.nn.functional as F
+    x = torch.rand(batch, 3, img, img, device='cuda')
+    out = {}
+    for size in sizes:
+        mid = torch.empty(batch, 3, size, size, device='cuda')
+        s2d = torch.empty(batch, size // 2, size // 2, 16, dtype=torch.bfloat16, device='cuda')
+        parts = {
+            "interpolate": lambda: F.interpolate(x, size=(size, size), mode='bilinear', align_corners=False),
+            "resize_bilinear": lambda: hipk.resize_bilinear(x, mid),
+            "input_s2d": lambda: hipk.input_s2d(mid, s2d),
+            "a_interpolate_then_s2d": lambda: hipk.input_s2d(F.interpolate(x, size=(size, size), mode='bilinear', align_corners=False), s2d),
+            "b_resize_then_s2d": lambda: (hipk.resize_bilinear(x, mid), hipk.input_s2d(mid, s2d)),
+            "c_resize_s2d_fused": lambda: hipk.resize_bilinear_s2d(x, s2d),
+        }
+        ms = {k: [] for k in parts}
+        for _ in range(reps):
+            for k, fn in parts.items():                                                  # alternate
+                ms[k].append(_timed(fn))
+        in_b, mid_b, out_b = x.numel() * 4, mid.numel() * 4, s2d.numel() * 2
+        moved = {"interpolate": in_b + mid_b, "resize_bilinear": in_b + mid_b, "input_s2d": mid_b + out_b,
+                 "a_interpolate_then_s2d": in_b + 2 * mid_b + out_b, "b_resize_then_s2d": in_b + 2 * mid_b + out_b,
+                 "c_resize_s2d_fused": in_b + out_b}
+        entry = {}
+        for k, v in ms.items():
+            med = statistics.median(v)
+            entry[k] = {"ms": med, "ms_all": v, "bytes_moved": moved[k], "GB_per_s": moved[k] / med / 1e6,
+                        "share_of_hbm_peak": moved[k] / (med * 1e-3) / HBM_PEAK_B_PER_S}
+        out[f"{img}_to_{size}"] = entry
+        print(json.dumps({f"{img}_to_{size}": {k: round(e["ms"], 4) for k, e in entry.items()}}), flush=True)
+        del mid, s2d
+    return out
+
+
+def program_build_cost(batch, sizes):
+    """seconds of the first training step (forward, loss-free backward) of YOLOv5s at a shape the model has not run, which builds
+    the program, its training buffers and its backward, against the median of five later steps"""
+    from yoloseries_amd import models
+    torch.manual_seed(0)
+    m = models.YOLOV5Small(3, 80).cuda().train()
+    m._yh_program_budget_bytes = 1 << 50
+    out = {}
+    for size in sizes:
+        x = torch.rand(batch, 3, size, size, device='cuda')
+        times = []
+        for _ in range(6):
+            for p_ in m.parameters():
+                p_.grad = None
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sum((o.float() ** 2).mean() for o in m(x)).backward()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        prog = m._yh_state()['progs'][(batch, size, size)]
+        out[str(size)] = {"first_step_s": times[0], "later_step_s": statistics.median(times[1:]), "later_all_s": times[1:],
+                          "program_owned_bytes": prog.owned_bytes()}
+        print(json.dumps({f"program_{size}": out[str(size)]}), flush=True)
+        m._yh_state()['progs'].clear()
+        del prog, x
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--multiscale", action="store_true")
+    ap.add_argument("--sizes", type=int, nargs="+", default=[320, 608, 960])
+    ap.add_argument("--program-sizes", type=int, nargs="*", default=[640, 960])
     ap.add_argument("--src", type=int, nargs=2, default=[480, 640])
     ap.add_argument("--img", type=int, default=640)
     ap.add_argument("--batch", type=int, default=64)
@@ -79,6 +167,16 @@ def main():
     ap.add_argument("--device-batches", type=int, default=4, help="batches per worker (at least one) in a device-path run")
     ap.add_argument("--out")
     args = ap.parse_args()
+    if args.multiscale:
+        res = {"box": torch.cuda.get_device_name(0), "img": args.img, "batch": args.batch, "reps": args.reps,
+               "hbm_peak_B_per_s": HBM_PEAK_B_PER_S, "resize": multiscale_rates(args.img, args.batch, args.sizes, args.reps),
+               "program_build": program_build_cost(args.batch, args.program_sizes)}
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     res = {"box": torch.cuda.get_device_name(0), "cpus": len(os.sched_getaffinity(0)), "src_hw": args.src, "img": args.img, "batch": args.batch,
            "reps": args.reps, "kernel": kernel_rate(tuple(args.src), args.img, args.batch, args.reps), "loader_img_per_s": {}}
     print(json.dumps({"kernel": res["kernel"]}), flush=True)

@@ -30,6 +30,7 @@ from yoloseries_amd.trainer import ExponentialMovingAverageModel, YOLOV5Evaluato
 from yoloseries_amd.utils import FlatSGD, mAP_v2                                    # noqa: E402
 from yoloseries_amd.utils.dist import (DataParallelGrads, all_reduce_norm, get_local_rank, get_rank, get_world_size,
                                        synchronize)                                # noqa: E402
+from yoloseries_amd.utils.multiscale import draw_multiscale_shape                   # noqa: E402
 from yoloseries_amd.utils.synth import COCO_ANCHORS, synth_shapes_batch, synth_targets      # noqa: E402
 
 
@@ -99,6 +100,7 @@ class Training:
         self.is_distributed = get_world_size() > 1
         self.cwd = Path('./').absolute()
         self.history = []
+        self.size_history = []            # multi-scale training: the [h, w] each step ran at
         self.before_train()
 
     # ------------------------------------------------------------------ set-up (train_yolov5.py:166-256)
@@ -133,6 +135,15 @@ class Training:
         self.accumulate = max(1, round(hyp['accumulate_loss_step'] / hyp['batch_size'] / get_world_size()))
         self.validate = self.build_evaluator(self.model)
         self.start_epoch = hyp.get('start_epoch', 0)
+        if hyp.get('mutil_scale_training', False):
+            # ~20 shapes instead of one: the engine's program cache turns least-recently-used under a byte budget (engine/module.py)
+            budget = hyp.get('multi_scale_budget_gb')
+            if budget is None:
+                budget = MULTI_SCALE_FREE_FRACTION * torch.cuda.mem_get_info(self.device)[0] / 2 ** 30
+            self.model._yh_program_budget_bytes = int(float(budget) * 2 ** 30)
+            if self.rank == 0:
+                print(f"multi-scale training: sizes {max(hyp['input_img_size']) // 2 // 32 * 32}..{int(max(hyp['input_img_size']) * 1.5) // 32 * 32}, "
+                      f"program cache budget {self.model._yh_program_budget_bytes / 2 ** 30:.2f} GiB", flush=True)
         if hyp.get('pretrained_model_path'):
             self.load_model(hyp['pretrained_model_path'])
 
@@ -189,11 +200,21 @@ class Training:
                 boundary = (i + 1) % self.accumulate == 0
                 ctx = self.dp.no_sync() if (self.dp is not None and not boundary) else _Null()
                 with ctx:
+                    new_shape = None
+                    if hyp.get('mutil_scale_training', False):
+                        # train_yolov5.py:321,526-544; the images are resized as the model ingests them, and the loss runs at the
+                        # step's size (the reference normalises by the configured one: DESIGN.md section 4).  Before anything reads
+                        # the targets or the loss's size
+                        scale, new_shape = draw_multiscale_shape(hyp['input_img_size'], x['img'].shape[2:])
+                        if scale != 1.:
+                            x['ann'][:, :, :4] *= scale
+                        self.loss_fcn.set_input_img_size(new_shape)
+                        self.size_history.append(list(new_shape))
                     if hyp.get('prefetch_assign', False):
                         # the target assignment on a side stream beside the forward pass (it needs the targets only); measured on the
                         # YOLOv5s step it does not pay (profiles/r04_step_experiments.txt, r): off unless the configuration asks for it
                         self.loss_fcn.prefetch_assign(x['ann'])
-                    stage_preds = self.model(x['img'])
+                    stage_preds = self.model(x['img']) if new_shape is None else self.model(x['img'], input_size=new_shape)
                     loss_dict = self.loss_fcn(stage_preds, x['ann'])
                     loss_dict['tot_loss'].backward()
                 if boundary:
@@ -208,6 +229,8 @@ class Training:
                     h = self.history[-1]
                     print(f"epoch {epoch + 1}/{hyp['total_epoch']} step {i + 1}/{len(self.train_dataloader)} "
                           f"{self.log_line(h)} lr {self.optimizer.param_groups[0]['lr']:.5f}", flush=True)
+            if self.rank == 0 and self.size_history:
+                print(f"multi-scale sizes of epoch {epoch + 1}: {self.size_history[-len(self.train_dataloader):]}", flush=True)
             self.save_model(epoch + 1, step_in_total=step_in_total, loss_dict=self.history[-1])
             if (epoch + 1) % hyp['validation_every'] == 0:
                 self.after_epoch(epoch + 1)
@@ -265,6 +288,9 @@ class Training:
         return state
 
 
+MULTI_SCALE_FREE_FRACTION = 0.5       # default program-cache budget of --multi-scale: this share of the free device memory
+
+
 class _Null:
     def __enter__(self):
         return self
@@ -288,6 +314,12 @@ def main(argv=None, training_cls=None, default_cfg=None):
                     "two runs on the same seed and data write the same checkpoint")
     ap.add_argument("--device-letterbox", action="store_true", help="with --data dataset: the loader's workers ship the raw uint8 images "
                     "and one HIP kernel letterboxes and normalises the batch on the GPU (same batches, bit for bit)")
+    ap.add_argument("--multi-scale", action="store_true", help="the reference's mutil_scale_training: every step draws a side length "
+                    "in [0.5, 1.5] x --img (a multiple of 32), the batch is resized on the GPU as the model ingests it, the targets are "
+                    "scaled and the loss runs at that size; evaluation stays at --img")
+    ap.add_argument("--multi-scale-budget-gb", type=float, help="with --multi-scale: GiB of device memory that the cached per-shape "
+                    f"programs (activation and gradient buffers) may hold; least-recently-used shapes are rebuilt when they return. "
+                    f"Default: {MULTI_SCALE_FREE_FRACTION:.0%} of the device memory free when training starts")
     args = ap.parse_args(argv)
     if args.deterministic:                                               # before any model / program is built
         import yoloseries_amd
@@ -307,6 +339,8 @@ def main(argv=None, training_cls=None, default_cfg=None):
             ap.error(f"--device-letterbox needs --data dataset: --data {hyp.get('data_source', 'tensor')} generates batches that already "
                      "have the network's size, so there are no images to letterbox")
         hyp['device_letterbox'] = True
+    if args.multi_scale: hyp['mutil_scale_training'] = True              # noqa: E701
+    if args.multi_scale_budget_gb is not None: hyp['multi_scale_budget_gb'] = args.multi_scale_budget_gb   # noqa: E701
     if training_cls is not None:                                         # train_yolox.py:808: Training(hyp)
         t = training_cls(hyp)
     else:

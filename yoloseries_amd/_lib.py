@@ -178,6 +178,8 @@ _SIGS = {
     "yh_input_s2d": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "yh_fill_u32": (_i32, [_vp, C.c_uint32, _i64, _vp]),
     "yh_letterbox_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "yh_resize_bilinear": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "yh_resize_bilinear_s2d": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "yh_pack_bf16": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "yh_gather_f32": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "yh_sgd_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _f32, _i32, _i32, _vp, _vp]),

@@ -69,6 +69,25 @@ class _NetFn(torch.autograd.Function):
         return (None, None, gx, *pgrads)
 
 
+MAX_PROGRAMS = 4                # cached shapes per model when no byte budget is set
+
+
+def _evict_programs(progs, key, budget):
+    """Bound the program cache `progs` (a dict in insertion order) after a look-up of `key`.  budget None: at most MAX_PROGRAMS
+    entries, the one inserted first goes.  Otherwise `key` moves to the warm end and the coldest entries go until the owned bytes
+    fit `budget`; `key` itself is never dropped."""
+    if budget is None:
+        if len(progs) > MAX_PROGRAMS:      # bound the number of cached shapes
+            progs.pop(next(iter(progs)))
+        return
+    progs[key] = progs.pop(key)
+    total = sum(p.owned_bytes() for p in progs.values())
+    for k in list(progs):
+        if total <= budget or k == key:
+            break
+        total -= progs.pop(k).owned_bytes()
+
+
 class HipModuleMixin:
     """Mixed into nn.Modules whose forward runs on the engine."""
 
@@ -98,11 +117,17 @@ class HipModuleMixin:
 
     # subclasses implement:  _yh_build(builder, B, H, W) -> (input_kind, outputs)
     def _yh_program(self, B, H, W):
+        """The program of one (batch, input shape), built at first use and cached.  By default the cache holds four programs and
+        drops the one inserted first.  With `model._yh_program_budget_bytes` set (multi-scale training draws from ~20 shapes) the
+        order is least-recently-used and the bound is in bytes: after every look-up, programs are dropped from the cold end until
+        `Program.owned_bytes()` of the rest fits the budget; the one just asked for always stays, the count is not bounded.  The
+        ParamPack is shared by all programs and survives every eviction."""
         st = self._yh_state()
         if st['pack'] is not None and not st['pack'].valid_for(self):
             st = {'pack': None, 'progs': {}}
             self.__dict__['_yh'] = st
         key = (B, H, W)
+        budget = getattr(self, '_yh_program_budget_bytes', None)
         prog = st['progs'].get(key)
         if prog is None:
             b = Builder()
@@ -112,9 +137,29 @@ class HipModuleMixin:
             prog = Program(b, st['pack'], B, outputs)
             prog.in_buf = b.bufs[0]
             st['progs'][key] = prog
-            if len(st['progs']) > 4:      # bound the number of cached shapes
-                st['progs'].pop(next(iter(st['progs'])))
+        _evict_programs(st['progs'], key, budget)
         return prog
+
+    def _yh_ingest_plan(self, x, input_size=None):
+        """What a model's forward(x, input_size) does before it writes the stem's input: (program, contiguous fp32 image, whether
+        the image is resized on the way in).  The program is keyed on the size the network runs at."""
+        if not x.is_cuda:
+            raise RuntimeError("yoloseries_amd models run on an MI355X device only (no CPU path in the product)")
+        B, _, H, W = x.shape
+        Hn, Wn = (H, W) if input_size is None else (int(input_size[0]), int(input_size[1]))
+        resize = (Hn, Wn) != (H, W)
+        if resize and x.requires_grad and torch.is_grad_enabled():
+            raise YoloHipError(f"forward(x, input_size={[Hn, Wn]}) with x.requires_grad: there is no gradient through the resize; "
+                               "detach x, or resize it with differentiable torch ops and pass the result")
+        prog = self._yh_program(B, Hn, Wn)
+        xin = x.detach()
+        if xin.dtype != torch.float32 or not xin.is_contiguous():
+            xin = xin.float().contiguous()
+        return prog, xin, resize
+
+    def _yh_cached_bytes(self):
+        """device bytes owned by the cached programs (what `_yh_program_budget_bytes` bounds)"""
+        return sum(p.owned_bytes() for p in self._yh_state()['progs'].values())
 
     def _yh_outputs(self, prog):
         from ..layout import cell_major_view

@@ -244,6 +244,34 @@ def letterbox_batch(raw, img_off, src_hw, rows, cols, out, fill_value=128):
           "yh_letterbox_batch")
 
 
+def _resize_src(x, who):
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError(f"{who}: expected a contiguous (B, C, H, W) float32 tensor on the GPU, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    return x.shape
+
+
+def resize_bilinear(x, out):
+    """x (B, C, H, W) float32 -> out (B, C, Ho, Wo) float32 on the current stream: F.interpolate(bilinear, align_corners=False) of
+    torch's CPU build, bit for bit (utils/multiscale.py resize_bilinear_host states the arithmetic)"""
+    B, Ch, H, W = _resize_src(x, "resize_bilinear")
+    if (out.dim() != 4 or tuple(out.shape[:2]) != (B, Ch) or out.dtype != torch.float32 or out.device != x.device
+            or not out.is_contiguous()):
+        raise ValueError(f"resize_bilinear: expected a contiguous float32 output ({B}, {Ch}, Ho, Wo) on {x.device}, "
+                         f"got {out.dtype} {tuple(out.shape)} on {out.device}")
+    check(lib().yh_resize_bilinear(_p(x), B, Ch, H, W, out.shape[2], out.shape[3], _p(out), _st()), "yh_resize_bilinear")
+
+
+def resize_bilinear_s2d(x, out):
+    """x (B, Cin <= 4, H, W) float32 -> out (B, Ho/2, Wo/2, 16) bfloat16, the stem's input at the size (Ho, Wo): the bits of
+    input_s2d(resize_bilinear(x)) without the float32 intermediate"""
+    B, Cin, H, W = _resize_src(x, "resize_bilinear_s2d")
+    if (out.dim() != 4 or out.shape[0] != B or out.shape[3] != 16 or out.dtype != torch.bfloat16 or out.device != x.device
+            or not out.is_contiguous()):
+        raise ValueError(f"resize_bilinear_s2d: expected a contiguous bfloat16 output ({B}, Ho/2, Wo/2, 16) on {x.device}, "
+                         f"got {out.dtype} {tuple(out.shape)} on {out.device}")
+    check(lib().yh_resize_bilinear_s2d(_p(x), B, Cin, H, W, 2 * out.shape[1], 2 * out.shape[2], _p(out), _st()), "yh_resize_bilinear_s2d")
+
+
 def fill_zero(t):
     nbytes = t.numel() * t.element_size()
     assert nbytes % 4 == 0

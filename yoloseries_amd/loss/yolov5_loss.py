@@ -87,6 +87,13 @@ class YOLOV5Loss:
         self._anchors_host = [[[float(v) for v in a] for a in st] for st in anchors.detach().cpu().tolist()]
 
     # ---- state -----------------------------------------------------------------------------
+    def set_input_img_size(self, hw):
+        """The size [h, w] of the images behind the next predictions (multi-scale training: the size of the step).  Everything a
+        call derives from the size -- target normalisation, the anchors' grid scale, in __call__ and assign -- goes into a
+        descriptor built from this attribute when the call runs (nothing of an earlier size is kept); a NEW list is stored, so `hyp['input_img_size']`, which the evaluators share, keeps
+        the configured value.  (The reference normalises by the configured size whatever the step's: DESIGN.md section 4.)"""
+        self.input_img_size = [int(hw[0]), int(hw[1])]
+
     @property
     def balances(self):
         if self._balances is None:

@@ -92,6 +92,12 @@ class YOLOXLoss:
         pc = torch.sqrt(torch.sigmoid(torch.zeros(self.num_class)) * torch.sigmoid(torch.zeros(1)))
         self._cls_cost_const = float((-(t * torch.log(pc) + (1 - t) * torch.log(1 - pc))).sum(-1))
 
+    def set_input_img_size(self, hw):
+        """The size [h, w] of the images behind the next predictions (multi-scale training: the size of the step).  The stage
+        strides are img_sz[0] / h of each head, taken from this attribute at every call; a NEW list is stored, so
+        `hyp['input_img_size']`, which the evaluators share, keeps the configured value."""
+        self.img_sz = [int(hw[0]), int(hw[1])]
+
     @property
     def balances(self):
         if self._balances is None:

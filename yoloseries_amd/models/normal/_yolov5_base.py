@@ -106,15 +106,15 @@ class YOLOV5Base(HipModuleMixin, nn.Module):
         large_x = self.head_stage4_bscp._emit(b, "head_stage4_bscp.", [x, head1_x])
         return self.detect._emit(b, "detect.", [small_x, mid_x, large_x])
 
-    def forward(self, x):
+    def forward(self, x, input_size=None):
         """:param x: (bn, 3, H, W) float, H and W multiples of 32
+        :param input_size: (Ho, Wo), multiples of 32: run the network on `x` resized to that size (bilinear, align_corners=False:
+            the multi-scale training of utils/multiscale.py).  The resize happens while the stem's input is written
+            (yh_resize_bilinear_s2d), the program is the one of (bn, Ho, Wo), and no gradient flows to `x`.
         :return: (small, mid, large) each (bn, A*(5+nc), H/s, W/s), bf16, cell-major memory"""
-        if not x.is_cuda:
-            raise RuntimeError("yoloseries_amd models run on an MI355X device only (no CPU path in the product)")
-        B, Cin, H, W = x.shape
-        prog = self._yh_program(B, H, W)
-        xin = x.detach()
-        if xin.dtype != torch.float32 or not xin.is_contiguous():
-            xin = xin.float().contiguous()
-        hipk.input_s2d(xin, prog.in_buf.t)
+        prog, xin, resize = self._yh_ingest_plan(x, input_size)
+        if resize:
+            hipk.resize_bilinear_s2d(xin, prog.in_buf.t)
+        else:
+            hipk.input_s2d(xin, prog.in_buf.t)
         return self._yh_forward(prog, x)

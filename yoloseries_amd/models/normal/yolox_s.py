@@ -141,15 +141,14 @@ class YOLOXSmall(HipModuleMixin, nn.Module):
             outs.append(o.y.t.as_strided((Bn, 1, E, h, w), (h * w * ld, h * w * ld, 1, w * ld, ld)))
         return outs
 
-    def forward(self, x):
-        """:return: OrderedDict pred_s / pred_m / pred_l, each (bn, num_anchors, 5+nc, H/s, W/s) [x, y, w, h, cof, cls...]"""
-        if not x.is_cuda:
-            raise RuntimeError("yoloseries_amd models run on an MI355X device only (no CPU path in the product)")
-        B, Cin, H, W = x.shape
-        prog = self._yh_program(B, H, W)
-        xin = x.detach()
-        if xin.dtype != torch.float32 or not xin.is_contiguous():
-            xin = xin.float().contiguous()
-        hipk.input_s2d(xin, prog.in_buf.t)
+    def forward(self, x, input_size=None):
+        """:param input_size: (Ho, Wo), multiples of 32: run the network on `x` resized to that size (bilinear, align_corners=False),
+            the resize fused into the write of the stem's input; no gradient flows to `x` then (utils/multiscale.py)
+        :return: OrderedDict pred_s / pred_m / pred_l, each (bn, num_anchors, 5+nc, H/s, W/s) [x, y, w, h, cof, cls...]"""
+        prog, xin, resize = self._yh_ingest_plan(x, input_size)
+        if resize:
+            hipk.resize_bilinear_s2d(xin, prog.in_buf.t)
+        else:
+            hipk.input_s2d(xin, prog.in_buf.t)
         s, m, l = self._yh_forward(prog, x)
         return OrderedDict((("pred_s", s), ("pred_m", m), ("pred_l", l)))
