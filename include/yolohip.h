@@ -340,6 +340,30 @@ int yh_resize_bilinear(const float* x, int B, int C, int H, int W, int Ho, int W
  * order, zero padding and fp32 -> bf16 conversion; equal to yh_input_s2d(yh_resize_bilinear(x)) bit for bit with no fp32
  * intermediate in memory.  Ho and Wo even; out 16-byte aligned.                                                               */
 int yh_resize_bilinear_s2d(const float* x, int B, int Cin, int H, int W, int Ho, int Wo, yh_bf16* out, yh_stream stream);
+/* train-time augmentation of a batch of raw images (utils/data_aug.py: mosaic :579-671, RandomPerspective :482-576, RandomHSV
+ * :363-389, RandomFlipLR/UD :434-478 of the reference, per image on the host there) as one gather per output pixel.  The canvas
+ * that the reference pastes (up to) four images into is described, not built: */
+typedef struct yh_aug_tile {      /* one pasted image of the (virtual) canvas */
+    int64_t off;                  /* byte offset of the image in `raw` (HWC uint8, any alignment) */
+    int32_t src_h, src_w;
+    int32_t sx0, sy0;             /* source pixel shown at the rectangle's top-left corner */
+    int32_t ox0, oy0, ox1, oy1;   /* paste rectangle in canvas pixels, half open; empty = unused tile */
+} yh_aug_tile;
+/* Output pixel (x, y) of image b samples the canvas at (u, v) = ((m0 x + m1 y + m2) / w, (m3 x + m4 y + m5) / w),
+ * w = m6 x + m7 y + m8 (pixel i at coordinate i, OpenCV's convention), bilinearly in fp32 from the taps floor(u) + {0, 1},
+ * floor(v) + {0, 1}.  A tap inside the canvas and inside a tile's rectangle is that tile's byte at
+ * (sy0 + ty - oy0, sx0 + tx - ox0) (the highest tile index wins where rectangles overlap); every other tap is fill_value.
+ * hsv_gain (NULL = off) multiplies hue / saturation / value of the blended pixel (float HSV on OpenCV's 8-bit scales); the
+ * result / 255 is stored.  yoloseries_amd/csrc/augment.hip lists the operation order, utils/augment.py augment_batch_host is the
+ * same computation in NumPy, bit for bit.
+ * tiles [B][4], canvas_hw [B][2] = {h, w}, minv [B][9] row major, hsv_gain [B][3].  The caller owns the validity of the tables
+ * (dataset/data_collater.py augment_collate_fn checks them): rectangles inside their canvas, source windows inside their images,
+ * images inside raw, raw at least 3 bytes (a tap that shows the fill value reads bytes 0..2 and drops them).  Source indices are
+ * clamped into [0, src_h) x [0, src_w) all the same.  W % 4 == 0, out 16-byte aligned, tiles 8-byte aligned,
+ * 0 <= fill_value <= 255.                                                                                                  */
+int yh_augment_batch(const uint8_t* raw, const yh_aug_tile* tiles /* [B][4] */, const int32_t* canvas_hw /* [B][2] */,
+                     const float* minv /* [B][9] output pixel -> canvas, row major */, const float* hsv_gain /* [B][3]; NULL = off */,
+                     int B, int H, int W, int fill_value, float* out /* (B,3,H,W) */, yh_stream stream);
 
 /* ------------------------------------------------------------------------ *
  * Parameter arena: gather/scatter between the fp32 master parameters and the

@@ -16,6 +16,13 @@ runs of 20 launches after 5 warm-ups, with the bytes each route has to move and 
 and what a miss of the program cache costs: the first training step of YOLOv5s at a shape it has not seen, against a later one.
 
     python tools/bench_ingest.py --multiscale [--img 640] [--batch 64] [--sizes 320 608 960] [--out profiles/ingest_multiscale.json]
+
+--augment measures the augmentation kernel (hipk.augment_batch: mosaic + warp + flips + HSV in one launch): --batch outputs of
+--img x --img from 2 --img x 2 --img mosaic canvases of four --src images each, plans drawn with the shipped data_aug_* values, events
+around 50 launches after 10 warm-ups, medians of --reps runs alternating with its variants (HSV off; affine, i.e. no divide; a canvas
+with no tile, i.e. the stores alone) and with the letterbox kernel at the same output size, which is the comparison.
+
+    python tools/bench_ingest.py --augment [--src 480 640] [--img 640] [--batch 64] [--out profiles/ingest_augment.json]
 """
 import argparse
 import json
@@ -74,6 +81,45 @@ def kernel_rate(src_hw, img, batch, reps):
             "output_TB_per_s": nbytes / med / 1e9, "images_per_s": batch / med * 1e3,
             "border_only_ms_per_launch": statistics.median(ms["border_only"]),
             "border_only_output_TB_per_s": nbytes / statistics.median(ms["border_only"]) / 1e9}
+
+
+def augment_rate(src_hw, img, batch, reps):
+    import random
+    import numpy as np
+    from yoloseries_amd.utils import augment as A
+    ds = SyntheticDetectionDataset(16, img_hw=src_hw, seed=5)
+    items = [ds[i] for i in range(len(ds))]
+    hyp = A.check_aug_hyp({})                                                         # the shipped values (config/train_yolov5.yaml)
+    rng, np_rng = random.Random(5), np.random.RandomState(5)
+
+    def tables(hyp):
+        plans = [A.draw_plan(b % len(items), len(items), lambda i: items[i][0].shape[:2], [img, img], hyp, rng, np_rng) for b in range(batch)]
+        raw, tiles, canvas_hw, minv, gains = A.plan_tables(plans, [[items[i][0] for i in p['indices']] for p in plans])
+        dev = [torch.from_numpy(raw).cuda(), torch.from_numpy(tiles.view(np.uint8).reshape(batch, 4, 40)).cuda(),
+               torch.from_numpy(canvas_hw).cuda(), torch.from_numpy(minv).cuda(), None if gains is None else torch.from_numpy(gains).cuda()]
+        return dev
+
+    full = tables(hyp)
+    affine = tables(dict(hyp, data_aug_prespective=0.0))
+    variants = {"shipped": full, "hsv_off": full[:4] + [None], "affine": affine, "affine_hsv_off": affine[:4] + [None],
+                "no_tile": [full[0], torch.zeros_like(full[1]), full[2], full[3], None]}
+    out = torch.empty(batch, 3, img, img, device='cuda')
+    lb_host = raw_imgsize_collate_fn([items[b % len(items)] for b in range(batch)], dst_size=[img, img])
+    lb = [lb_host[k].cuda() for k in ('raw', 'img_off', 'src_hw', 'rows', 'cols')]
+    fns = {k: (lambda v=v: hipk.augment_batch(*v, out, hyp['data_aug_fill_value'])) for k, v in variants.items()}
+    fns["letterbox"] = lambda: hipk.letterbox_batch(*lb, out)
+    ms = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():                                                        # alternate
+            ms[k].append(_timed(fn, launches=50, warmup=10))
+    nbytes = out.numel() * 4
+    res = {"output_bytes": nbytes, "source_bytes": full[0].numel(), "canvas": [2 * img, 2 * img]}
+    for k, v in ms.items():
+        med = statistics.median(v)
+        res[k] = {"ms_per_launch": med, "ms_all": v, "output_TB_per_s": nbytes / med / 1e9, "images_per_s": batch / med * 1e3}
+    for k in variants:
+        res[k]["over_letterbox"] = res[k]["ms_per_launch"] / res["letterbox"]["ms_per_launch"]
+    return res
 
 
 HBM_PEAK_B_PER_S = 8e12             # MI355X specification; about 6.3e12 is achievable by a streaming kernel
@@ -156,6 +202,7 @@ def program_build_cost(batch, sizes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--multiscale", action="store_true")
+    ap.add_argument("--augment", action="store_true")
     ap.add_argument("--sizes", type=int, nargs="+", default=[320, 608, 960])
     ap.add_argument("--program-sizes", type=int, nargs="*", default=[640, 960])
     ap.add_argument("--src", type=int, nargs=2, default=[480, 640])
@@ -167,6 +214,15 @@ def main():
     ap.add_argument("--device-batches", type=int, default=4, help="batches per worker (at least one) in a device-path run")
     ap.add_argument("--out")
     args = ap.parse_args()
+    if args.augment:
+        res = {"box": torch.cuda.get_device_name(0), "src_hw": args.src, "img": args.img, "batch": args.batch, "reps": args.reps,
+               "kernel": augment_rate(tuple(args.src), args.img, args.batch, args.reps)}
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     if args.multiscale:
         res = {"box": torch.cuda.get_device_name(0), "img": args.img, "batch": args.batch, "reps": args.reps,
                "hbm_peak_B_per_s": HBM_PEAK_B_PER_S, "resize": multiscale_rates(args.img, args.batch, args.sizes, args.reps),

@@ -61,20 +61,34 @@ class PrefetchedDataset:
     """the reference's data path on a synthetic dataset: torch DataLoader -> fixed_imgsize_collate_fn
     (dataset/data_collater.py:20-64) -> DataPrefetcher (dataset/data_prefetcher.py:6-56, train_yolov5.py:458-497).
     device_letterbox=True: the workers ship the uint8 images (raw_imgsize_collate_fn) and DeviceLetterboxPrefetcher letterboxes
-    and normalises them on the GPU; the batches are the same bit for bit."""
+    and normalises them on the GPU; the batches are the same bit for bit.
+    aug_hyp (the data_aug_* keys): the reference's enable_data_aug path (build_dataloader(enable_data_aug=True) builds the same
+    trio): the workers draw the augmentation plans and DeviceAugmentPrefetcher produces mosaic, warp, HSV and flips on the GPU, until
+    close_data_aug()."""
 
-    def __init__(self, steps, batch, img, num_class, seed, workers=0, device_letterbox=False):
+    def __init__(self, steps, batch, img, num_class, seed, workers=0, device_letterbox=False, aug_hyp=None):
         from functools import partial
         from torch.utils.data import DataLoader
         from yoloseries_amd.dataset import (DataPrefetcher, DeviceLetterboxPrefetcher, SyntheticDetectionDataset, fixed_imgsize_collate_fn,
                                             raw_imgsize_collate_fn)
         self._prefetcher = DeviceLetterboxPrefetcher if device_letterbox else DataPrefetcher
         ds = SyntheticDetectionDataset(steps * batch, img_hw=(int(img * 0.75) // 8 * 8, img), num_class=num_class, seed=seed)
+        self.dataset = ds
+        if aug_hyp is not None:
+            from yoloseries_amd.dataset import AugmentedDataset, DeviceAugmentPrefetcher, augment_collate_fn
+            self.dataset = AugmentedDataset(ds, [img, img], aug_hyp, seed=seed)
+            self._prefetcher = partial(DeviceAugmentPrefetcher, fill_value=self.dataset.hyp['data_aug_fill_value'])
+            self.loader = DataLoader(self.dataset, batch_size=batch, shuffle=False, num_workers=workers, drop_last=True, pin_memory=True,
+                                     collate_fn=partial(augment_collate_fn, dst_size=[img, img]))
+            return
         self.loader = DataLoader(ds, batch_size=batch, shuffle=False, num_workers=workers, drop_last=True, pin_memory=True,
                                  collate_fn=partial(raw_imgsize_collate_fn if device_letterbox else fixed_imgsize_collate_fn, dst_size=[img, img]))
 
     def __len__(self):
         return len(self.loader)
+
+    def close_data_aug(self):
+        self.dataset.close_data_aug()
 
     def __iter__(self):
         pf = self._prefetcher(self.loader)
@@ -118,7 +132,8 @@ class Training:
         if hyp.get('data_source', 'tensor') == 'dataset':
             dlb = bool(hyp.get('device_letterbox', False))
             self.train_dataloader = PrefetchedDataset(hyp['steps_per_epoch'], hyp['batch_size'], img, hyp['num_class'], 1 + self.rank,
-                                                      hyp.get('num_workers', 0), device_letterbox=dlb)
+                                                      hyp.get('num_workers', 0), device_letterbox=dlb,
+                                                      aug_hyp=hyp if hyp.get('enable_data_aug', False) else None)
             self.val_dataloader = PrefetchedDataset(hyp['val_batches'], hyp['batch_size'], img, hyp['num_class'], 101 + self.rank,
                                                     device_letterbox=dlb)
         else:
@@ -188,6 +203,10 @@ class Training:
         step_in_total = self.start_epoch * len(self.train_dataloader)
         for epoch in range(self.start_epoch, hyp['total_epoch']):
             self.model.train()
+            if hyp.get('enable_data_aug', False) and epoch == hyp['total_epoch'] - hyp['no_data_aug_epoch']:   # train_yolov5.py:289-293
+                self.train_dataloader.close_data_aug()
+                if self.rank == 0:
+                    print(f"epoch {epoch + 1}/{hyp['total_epoch']}: data augmentation closed", flush=True)
             # LambdaLR semantics (train_yolov5.py:152-164): 'initial_lr' stays the base learning rate, the per-epoch factor only
             # scales 'lr'; the warm-up interpolates towards the unscheduled 'initial_lr' (train_yolov5.py:437-456)
             base = self.lr_scheduler_fn(epoch)
@@ -314,6 +333,9 @@ def main(argv=None, training_cls=None, default_cfg=None):
                     "two runs on the same seed and data write the same checkpoint")
     ap.add_argument("--device-letterbox", action="store_true", help="with --data dataset: the loader's workers ship the raw uint8 images "
                     "and one HIP kernel letterboxes and normalises the batch on the GPU (same batches, bit for bit)")
+    ap.add_argument("--augment", action="store_true", help="with --data dataset: the reference's enable_data_aug (mosaic, random "
+                    "perspective, HSV, flips by the data_aug_* keys of the configuration), the pixels produced by one HIP kernel on the GPU; "
+                    "switched off for the last no_data_aug_epoch epochs")
     ap.add_argument("--multi-scale", action="store_true", help="the reference's mutil_scale_training: every step draws a side length "
                     "in [0.5, 1.5] x --img (a multiple of 32), the batch is resized on the GPU as the model ingests it, the targets are "
                     "scaled and the loss runs at that size; evaluation stays at --img")
@@ -339,6 +361,14 @@ def main(argv=None, training_cls=None, default_cfg=None):
             ap.error(f"--device-letterbox needs --data dataset: --data {hyp.get('data_source', 'tensor')} generates batches that already "
                      "have the network's size, so there are no images to letterbox")
         hyp['device_letterbox'] = True
+    if args.augment:
+        hyp['enable_data_aug'] = True
+    if hyp.get('enable_data_aug', False):
+        if hyp.get('data_source', 'tensor') != 'dataset':
+            ap.error(f"--augment (enable_data_aug) needs --data dataset: --data {hyp.get('data_source', 'tensor')} generates batches, there "
+                     "are no images to augment")
+        if hyp.get('device_letterbox', False):
+            ap.error("--augment and --device-letterbox are two ingest paths: the augmentation already runs on the device")
     if args.multi_scale: hyp['mutil_scale_training'] = True              # noqa: E701
     if args.multi_scale_budget_gb is not None: hyp['multi_scale_budget_gb'] = args.multi_scale_budget_gb   # noqa: E701
     if training_cls is not None:                                         # train_yolox.py:808: Training(hyp)

@@ -108,6 +108,12 @@ class ViewXform(C.Structure):
     _fields_ = [("scale", C.c_float), ("flip_axis", C.c_int32), ("img_h", C.c_float), ("img_w", C.c_float)]
 
 
+class AugTile(C.Structure):
+    """yh_aug_tile: one pasted image of the virtual mosaic canvas (yh_augment_batch); utils/augment.py TILE_DTYPE is its NumPy form"""
+    _fields_ = [("off", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("sx0", C.c_int32), ("sy0", C.c_int32),
+                ("ox0", C.c_int32), ("oy0", C.c_int32), ("ox1", C.c_int32), ("oy1", C.c_int32)]
+
+
 class BnFoldItem(C.Structure):
     _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("rm", C.c_void_p), ("rv", C.c_void_p),
                 ("scale", C.c_void_p), ("shift", C.c_void_p), ("eps", C.c_float), ("C", C.c_int32)]
@@ -180,6 +186,7 @@ _SIGS = {
     "yh_letterbox_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "yh_resize_bilinear": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "yh_resize_bilinear_s2d": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "yh_augment_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "yh_pack_bf16": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "yh_gather_f32": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "yh_sgd_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _f32, _i32, _i32, _vp, _vp]),

@@ -13,7 +13,7 @@ import torch
 from ..utils.letterbox import letter_resize_bbox, letter_resize_img, pack_raw_batch
 
 __all__ = ['fixed_imgsize_collate_fn', 'test_dataset_collate_fn', 'normal_normalization', 'raw_imgsize_collate_fn',
-           'raw_test_collate_fn']
+           'raw_test_collate_fn', 'augment_collate_fn']
 
 
 def normal_normalization(img):
@@ -86,3 +86,43 @@ def raw_test_collate_fn(data_in, dst_size):
     batch, infos = _raw_batch(list(data_in), dst_size)
     batch['resize_info'] = infos
     return batch
+
+
+def _box_rows(boxes, classes, index):
+    """(n, 6) float32 rows of one image from boxes that are already in the network input's frame"""
+    n = len(classes)
+    rows = torch.empty(n, 6)
+    if n:
+        rows[:, :4] = torch.from_numpy(np.asarray(boxes, dtype=np.float64).reshape(n, 4)).float()
+        rows[:, 4] = torch.as_tensor([float(c) for c in classes])
+        rows[:, 5] = float(index)
+    return rows
+
+
+def augment_collate_fn(data_in, dst_size):
+    """collate of AugmentedDataset (dataset/augmented.py) for DeviceAugmentPrefetcher.  Items: ([raw uint8 images], plan, labels in
+    the output frame, id), or the plain (image, annotation, id) of an un-augmented item, which becomes the letterbox as a plan
+    (utils/augment.py identity_plan), so one kernel serves the batch.  Out: the images concatenated ('raw') and the plan tables
+    ('tiles' as bytes (B, 4, 40), 'canvas_hw', 'minv', 'hsv_gain' or None), checked here (ValueError naming the image, before
+    anything is copied); 'ann', 'resize_info' and 'img_id' as fixed_imgsize_collate_fn builds them."""
+    from ..utils import augment as A
+    from ..utils.letterbox import letter_resize_bbox
+    plans, images, rows, infos, ids = [], [], [], [], []
+    for index, item in enumerate(data_in):
+        if len(item) == 4:
+            imgs, plan, ann, img_id = item
+            if tuple(plan['dst_hw']) != (int(dst_size[0]), int(dst_size[1])):
+                raise ValueError(f"image {index}: the plan was drawn for {plan['dst_hw']}, the batch is {list(dst_size)}")
+            rows.append(_box_rows(ann['bboxes'], ann['classes'], index))
+            infos.append({'augmented': True, 'M': plan['M_total'], 'org_shape': tuple(imgs[0].shape[:2])})
+        else:
+            img, ann, img_id = item
+            imgs, plan = [img], A.identity_plan(index, img.shape[:2], dst_size)
+            rows.append(_annotation_rows(ann, plan['record'], index))
+            infos.append(plan['record'])
+        plans.append(plan); images.append(imgs); ids.append(img_id)
+    raw, tiles, canvas_hw, minv, gains = A.plan_tables(plans, images)
+    return {'raw': torch.from_numpy(raw), 'tiles': torch.from_numpy(tiles.view(np.uint8).reshape(len(plans), 4, A.TILE_DTYPE.itemsize)),
+            'canvas_hw': torch.from_numpy(canvas_hw), 'minv': torch.from_numpy(minv),
+            'hsv_gain': None if gains is None else torch.from_numpy(gains), 'dst_size': (int(dst_size[0]), int(dst_size[1])),
+            'ann': _padded_annotations(rows), 'resize_info': infos, 'img_id': ids}

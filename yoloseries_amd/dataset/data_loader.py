@@ -1,8 +1,9 @@
 """build_dataloader / build_test_dataloader — the factory names the drivers import (dataset/data_loader.py:57-88, :156-179),
 returning the reference's (dataset, dataloader, prefetcher) triple.
 
-Reading image files and augmenting them (YOLODataset, Transforms, mosaic ...) is outside the hot-path scope (SURVEY §8:
-dataset tooling is out of scope, and OpenCV is absent from the image): `img_dir` is either the string "synthetic" — the
+Reading image files (YOLODataset) is outside the hot-path scope (dataset tooling is out of scope, and OpenCV is
+absent from the image); augmenting them (mosaic, RandomPerspective, RandomHSV, flips) is dataset/augmented.py + utils/augment.py,
+with the pixels produced on the GPU.  `img_dir` is either the string "synthetic" — the
 SyntheticDetectionDataset in the reference's __getitem__ format — or any object with __len__/__getitem__ yielding
 (image (h,w,3) uint8, {'bboxes': (n,4) xyxy, 'classes': [n]}, id) items, i.e. a user-supplied dataset; everything
 downstream of __getitem__ (fixed_imgsize_collate_fn -> letterbox -> DataPrefetcher) is the mirrored format path."""
@@ -12,8 +13,11 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
-from .data_collater import fixed_imgsize_collate_fn, raw_imgsize_collate_fn, raw_test_collate_fn, test_dataset_collate_fn
-from .data_prefetcher import DataPrefetcher, DeviceLetterboxPrefetcher, DeviceLetterboxTestPrefetcher, TestDataPrefetcher
+from .augmented import AugmentedDataset
+from .data_collater import (augment_collate_fn, fixed_imgsize_collate_fn, raw_imgsize_collate_fn, raw_test_collate_fn,
+                            test_dataset_collate_fn)
+from .data_prefetcher import (DataPrefetcher, DeviceAugmentPrefetcher, DeviceLetterboxPrefetcher, DeviceLetterboxTestPrefetcher,
+                              TestDataPrefetcher)
 from .synthetic import SyntheticDetectionDataset
 
 __all__ = ["build_dataloader", "build_val_dataloader", "build_test_dataloader"]
@@ -34,15 +38,33 @@ def _seed_worker(worker_id):
     np.random.seed((torch.initial_seed() + worker_id) % 2 ** 31)
 
 
+def _seed_worker_augment(worker_id):
+    """Python's `random` as well as NumPy's (the reference's augmentations draw from both); AugmentedDataset's own RNGs are seeded
+    from the worker's seed when the worker draws its first plan"""
+    import random
+    _seed_worker(worker_id)
+    random.seed(torch.initial_seed() + worker_id)
+
+
 def build_dataloader(img_dir, lab_dir, name_path, input_dim, aug_hyp, cache_num, enable_data_aug,
                      seed, batch_size, num_workers, pin_memory, shuffle, drop_last, device_letterbox=False):
     """training loader: DataLoader -> fixed_imgsize_collate_fn(dst_size=input_dim) -> DataPrefetcher on a GPU box.
     device_letterbox=True: the workers ship the uint8 images (raw_imgsize_collate_fn) and DeviceLetterboxPrefetcher letterboxes and
-    normalises them on the GPU; `prefetcher.next()` returns the same batches, bit for bit."""
-    if enable_data_aug:
-        raise NotImplementedError("data augmentation (utils/data_aug.py Transforms / mosaic) is outside the hot-path scope")
+    normalises them on the GPU; `prefetcher.next()` returns the same batches, bit for bit.
+    enable_data_aug=True: the dataset is wrapped in AugmentedDataset (plans drawn from the data_aug_* keys of `aug_hyp`: mosaic,
+    random perspective, HSV, flips), augment_collate_fn ships the raw images and the plan tables, and DeviceAugmentPrefetcher
+    produces the pixels on the GPU in one launch; `dataset.close_data_aug()` switches the augmentation off for later epochs."""
     dataset = _dataset_from(img_dir, input_dim, seed)
     gen = torch.Generator().manual_seed(seed if seed else 7)
+    if enable_data_aug:
+        if device_letterbox:
+            raise ValueError("enable_data_aug and device_letterbox are two ingest paths: the augmentation already runs on the device")
+        dataset = AugmentedDataset(dataset, input_dim, aug_hyp, seed=seed if seed else 7)
+        loader = DataLoader(dataset, batch_size=batch_size, shuffle=bool(shuffle), drop_last=bool(drop_last), num_workers=num_workers,
+                            pin_memory=bool(pin_memory), generator=gen, worker_init_fn=_seed_worker_augment,
+                            collate_fn=partial(augment_collate_fn, dst_size=input_dim))
+        fill = dataset.hyp['data_aug_fill_value']
+        return dataset, loader, (DeviceAugmentPrefetcher(loader, fill_value=fill) if torch.cuda.is_available() else None)
     loader = DataLoader(dataset, batch_size=batch_size, shuffle=bool(shuffle), drop_last=bool(drop_last), num_workers=num_workers,
                         pin_memory=bool(pin_memory), generator=gen, worker_init_fn=_seed_worker,
                         collate_fn=partial(raw_imgsize_collate_fn if device_letterbox else fixed_imgsize_collate_fn, dst_size=input_dim))

@@ -3,7 +3,7 @@ training loop, train_yolov5.py:458-497): while a step computes, the next batch i
 orders the compute stream behind that copy and marks the tensors as used on it."""
 import torch
 
-__all__ = ["DataPrefetcher", "TestDataPrefetcher", "DeviceLetterboxPrefetcher", "DeviceLetterboxTestPrefetcher"]
+__all__ = ["DataPrefetcher", "TestDataPrefetcher", "DeviceLetterboxPrefetcher", "DeviceLetterboxTestPrefetcher", "DeviceAugmentPrefetcher"]
 
 
 class _Prefetcher:
@@ -78,3 +78,27 @@ class DeviceLetterboxPrefetcher(_DeviceLetterbox):
 class DeviceLetterboxTestPrefetcher(_DeviceLetterbox):
     tensor_keys = ('img',)
     all_keys = ('img', 'resize_info')
+
+
+class DeviceAugmentPrefetcher(_Prefetcher):
+    """for loaders that collate with augment_collate_fn: the uint8 images and the plan tables are copied on the side stream and one
+    kernel (hipk.augment_batch: mosaic, warp, flips, HSV) writes 'img' there, into a fresh tensor for every batch.  `next()` returns
+    what DataPrefetcher returns."""
+    tensor_keys = ('img', 'ann')
+    all_keys = ('img', 'ann', 'resize_info', 'img_id')
+    raw_keys = ('raw', 'tiles', 'canvas_hw', 'minv')
+
+    def __init__(self, loader, fill_value=128):
+        self.fill_value = fill_value
+        super().__init__(loader)
+
+    def _stage(self, batch):
+        from .. import hipk
+        raw, tiles, canvas_hw, minv = (batch[k].cuda(non_blocking=True) for k in self.raw_keys)
+        gains = batch['hsv_gain'].cuda(non_blocking=True) if batch['hsv_gain'] is not None else None
+        H, W = batch['dst_size']
+        img = torch.empty(minv.shape[0], 3, H, W, dtype=torch.float32, device=raw.device)
+        hipk.augment_batch(raw, tiles, canvas_hw, minv, gains, img, self.fill_value)
+        out = {k: (batch[k].cuda(non_blocking=True) if k in self.tensor_keys else batch[k]) for k in self.all_keys if k != 'img'}
+        out['img'] = img
+        return out

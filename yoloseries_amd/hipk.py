@@ -244,6 +244,26 @@ def letterbox_batch(raw, img_off, src_hw, rows, cols, out, fill_value=128):
           "yh_letterbox_batch")
 
 
+def augment_batch(raw, tiles, canvas_hw, minv, hsv_gain, out, fill_value=128):
+    """raw uint8 images (concatenated HWC) + the plan tables of dataset/data_collater.py augment_collate_fn -> out (B, 3, H, W) float32
+    on the current stream: mosaic, warp, flips and HSV jitter in one launch (utils/augment.py augment_batch_host is the definition).
+    tiles: (B, 4, 40) uint8, the bytes of yh_aug_tile records; hsv_gain: (B, 3) float32 or None.  The tables' contents are the
+    caller's: the kernel reads raw wherever they point (inside the image they name)."""
+    B, _, H, W = out.shape
+    want = [(raw, torch.uint8, None), (tiles, torch.uint8, (B, 4, 40)), (canvas_hw, torch.int32, (B, 2)), (minv, torch.float32, (B, 9)),
+            (out, torch.float32, (B, 3, H, W))]
+    if hsv_gain is not None:
+        want.append((hsv_gain, torch.float32, (B, 3)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or not t.is_cuda or t.device != out.device or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"augment_batch: expected a contiguous {dtype} tensor of shape {shape or '(n,)'} on {out.device}, "
+                             f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if raw.numel() < 3:
+        raise ValueError(f"augment_batch: raw holds {raw.numel()} bytes, less than one pixel")
+    check(lib().yh_augment_batch(_p(raw), _p(tiles), _p(canvas_hw), _p(minv), _p(hsv_gain), B, H, W, int(fill_value), _p(out), _st()),
+          "yh_augment_batch")
+
+
 def _resize_src(x, who):
     if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
         raise ValueError(f"{who}: expected a contiguous (B, C, H, W) float32 tensor on the GPU, got {x.dtype} {tuple(x.shape)} on {x.device}")

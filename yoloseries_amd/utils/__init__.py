@@ -7,6 +7,7 @@ from .dist import *  # noqa: F401,F403
 from .mAP import mAP_v2  # noqa: F401
 from .letterbox import letter_resize_batch, letter_resize_bbox, letter_resize_img, letterbox_tables  # noqa: F401
 from .multiscale import bilinear_tables, draw_multiscale_shape, mutil_scale_training, resize_bilinear, resize_bilinear_host  # noqa: F401
+from .augment import augment_batch_host, draw_plan, hsv_jitter, plan_labels, plan_tables  # noqa: F401
 from .common import *  # noqa: F401,F403
 from .setup_env import *  # noqa: F401,F403
 from .gpu import *  # noqa: F401,F403
