@@ -139,6 +139,22 @@ int yh_conv_igemm(const yh_conv_desc* d, yh_stream stream);
 int yh_conv_kernel_name(const yh_conv_desc* d, char* buf, int buflen);
 /* rows of the bnr_part slab for this data-gradient descriptor; 0 = fused reduction not available for it */
 int yh_conv_bnr_rows(const yh_conv_desc* d);
+/* What yh_conv_igemm(d) will launch — family, rows of both slabs, instantiation — decided by the same plan: the three queries
+ * above in one call.  Needs no device and dereferences no operand.  Returns the rc yh_conv_igemm would return from its own argument
+ * checks; `out` is filled from the dims alone whenever they are positive (as yh_conv_stat_blocks answers), also beside a non-zero
+ * rc such as a null operand. */
+enum { YH_CONV_FAM_GENERIC = 0, YH_CONV_FAM_V2, YH_CONV_FAM_V3, YH_CONV_FAM_HALO, YH_CONV_FAM_HALO160, YH_CONV_FAM_STEM,
+       YH_CONV_FAM_DG2, YH_CONV_FAM_P3, YH_CONV_FAM_H80, YH_CONV_FAM_PW, YH_CONV_FAM_C80, YH_CONV_FAM_PT };
+typedef struct yh_conv_plan_info {
+    int32_t  family;                  /* YH_CONV_FAM_*: the kernel that runs (an algo that is not eligible falls back to the default) */
+    int32_t  variant;                 /* conv_v3_kernel: its tile, 1 = 256x128, 2 = 128x128, 3 = 128x64, 4 = 256x256; else 0 */
+    int32_t  tail;                    /* 1: the ragged-last-64-channel-block form of conv_v3_kernel / the halo kernels; siblings: 0 */
+    int32_t  stat_rows;               /* yh_conv_stat_blocks(d) */
+    int32_t  bnr_rows;                /* yh_conv_bnr_rows(d) */
+    int32_t  reserved;
+    char     name[96];                /* what yh_conv_kernel_name writes */
+} yh_conv_plan_info;
+int yh_conv_info(const yh_conv_desc* d, yh_conv_plan_info* out);
 
 /* Weight gradient: dW[n][tap*Ctot + coff_k + c] += sum_m gy[m][n] * X[src(m,tap)][c]
  * (fp32 atomics into a zeroed packed buffer).  One launch per input segment.

@@ -358,3 +358,42 @@ def test_wgrad_entries_at_judged_shapes(dev, chunk):
 def Program_wgrad_name(L, d):
     from yoloseries_amd.engine import Program
     return Program._wgrad_name(L, d)
+
+
+def test_engine_tunes_the_recorded_keys_from_its_candidates(dev, monkeypatch, tmp_path):
+    """the tuner on real engine descriptors (data gradients with the fused reduction, two-segment and upsampled layers, accumulation):
+    YOLOv5s at 2 x 128 x 128 with the shipped table off and an empty local one times every layer of a training forward, a backward
+    and an inference forward.  The keys it stores are those of tests/golden/tune_keys_v5s_2x128.json (recorded with this body on
+    the commit before the tuner read yh_conv_info; keys do not depend on timing, the stored choices do and are not compared), and
+    every stored conv choice is one of the candidates TunerMixin._conv_candidates listed for its key"""
+    import bench
+    from yoloseries_amd import models
+    from yoloseries_amd.engine import flags, tune
+    from yoloseries_amd.loss import YOLOV5Loss
+    from yoloseries_amd.utils.synth import COCO_ANCHORS, synth_targets
+    cache = tmp_path / "tune_cache.json"
+    monkeypatch.setenv("YH_TUNE_DEFAULTS", "0")
+    monkeypatch.setenv("YH_TUNE_CACHE", str(cache))
+    monkeypatch.setattr(tune._tune_cache, "data", None)
+    monkeypatch.setattr(flags, "TUNE_ITERS", 1)
+    lists, enumerate_ = {}, tune.TunerMixin._conv_candidates
+
+    def spy(L, d, kind):
+        cands = lists[tune.TunerMixin._conv_tune_key(d, kind, kind == "fwd")] = enumerate_(L, d, kind)
+        return cands
+    monkeypatch.setattr(tune.TunerMixin, "_conv_candidates", staticmethod(spy))
+    x = torch.rand(2, 3, 128, 128, generator=torch.Generator().manual_seed(5)).to(dev)
+    t = torch.from_numpy(synth_targets(2, 128, 80, 8, seed=6, min_boxes=4)).to(dev)
+    torch.manual_seed(0)
+    m = models.YOLOV5Small(3, 80).to(dev).train()
+    YOLOV5Loss(torch.from_numpy(COCO_ANCHORS).to(dev), bench.make_hyp(dev, 128, 2))(m(x), t)["tot_loss"].backward()
+    m.eval()
+    with torch.no_grad():
+        m(x)
+    torch.cuda.synchronize()
+    stored = json.load(open(cache))
+    assert sorted(stored) == json.load(open(os.path.join(ROOT, "tests", "golden", "tune_keys_v5s_2x128.json")))
+    conv = {k: v for k, v in stored.items() if k.startswith("conv")}
+    assert len(conv) >= 100 and set(conv) == set(lists)
+    for k, (tile_k, grid_cap, algo) in conv.items():
+        assert (algo, tile_k, grid_cap) in lists[k], (k, conv[k], lists[k])

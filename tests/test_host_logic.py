@@ -32,7 +32,8 @@ def test_ctypes_struct_sizes_match_header_layout(tmp_path):
     import ctypes as C
     import subprocess
     from yoloseries_amd import _lib
-    pairs = [("yh_seg", _lib.Seg), ("yh_conv_desc", _lib.ConvDesc), ("yh_wgrad_desc", _lib.WgradDesc), ("yh_wgrad_info", _lib.WgradInfo),
+    pairs = [("yh_seg", _lib.Seg), ("yh_conv_desc", _lib.ConvDesc), ("yh_conv_plan_info", _lib.ConvInfo), ("yh_wgrad_desc", _lib.WgradDesc),
+             ("yh_wgrad_info", _lib.WgradInfo),
              ("yh_v5loss_desc", _lib.V5LossDesc),
              ("yh_yolox_desc", _lib.YoloxDesc), ("yh_decode_desc", _lib.DecodeDesc), ("yh_bn_fold_item", _lib.BnFoldItem),
              ("yh_bn_part", _lib.BnPart), ("yh_cmd", _lib.Cmd)]
@@ -356,14 +357,10 @@ def test_conv_plan_table_is_stable():
     instantiations (`tools/conv_plan_table.py --digest`, taken from the library as it was before the planner was consolidated
     into conv_plan).  Planning is host code: no device needed.  A deliberate change of a plan — a new family, another tile —
     regenerates the record; `tools/conv_plan_table.py --reduced` prints the lines of a chunk that differs"""
-    import importlib.util
     import json
     from yoloseries_amd._lib import lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("conv_plan_table", os.path.join(root, "tools", "conv_plan_table.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    want = json.load(open(os.path.join(root, "tests", "golden", "conv_plan_digest.json")))
+    mod = _conv_plan_table()
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "conv_plan_digest.json")))
     got = mod.digest(mod.reduced(lib()), want["chunk"])
     assert want["lines"] >= 2500 and got["lines"] == want["lines"]
     assert got["names"] == want["names"], (sorted(set(got["names"]) - set(want["names"])), sorted(set(want["names"]) - set(got["names"])))
@@ -372,6 +369,165 @@ def test_conv_plan_table_is_stable():
     fams = {n.split("<")[0] for n in want["names"]}
     assert {"conv_stem_kernel", "conv_halo160_kernel", "conv_halo_kernel", "conv_v3_kernel", "conv_v2_kernel", "conv_igemm_kernel",
             "conv_dg2_kernel", "conv_p3_kernel", "conv_pt_kernel"} <= fams, fams
+
+
+def _conv_plan_table():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("conv_plan_table", os.path.join(ROOT, "tools", "conv_plan_table.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_conv_info_agrees_with_the_three_queries():
+    """yh_conv_info against yh_conv_kernel_name / yh_conv_stat_blocks / yh_conv_bnr_rows over the reduced corpus of
+    tools/conv_plan_table.py (the 530 shipped entries and 2 000 seeded random descriptors, invalid ones included): the same rc, the
+    same name where a name is given, the same rows always; a descriptor without operand pointers is refused and planned alike"""
+    import ctypes as C
+    import random
+    from yoloseries_amd import _lib
+    mod, L = _conv_plan_table(), _lib.lib()
+    cases = []
+    for _, f, (tile_k, grid_cap, algo) in mod.table_keys():
+        cases.append(dict(mod.case_of_key(f), tile_k=tile_k, grid_cap=grid_cap, algo=algo))
+    r = random.Random(20261016)
+    cases += [mod.random_case(r) for _ in range(2000)]
+    assert len(cases) == 2530
+    fams, refused = set(), 0
+    for c in cases:
+        d, o, buf = mod.make_desc(c), _lib.ConvInfo(), C.create_string_buffer(96)
+        rc = L.yh_conv_info(C.byref(d), C.byref(o))
+        assert rc == L.yh_conv_kernel_name(C.byref(d), buf, 96), c
+        assert rc != 0 or (o.name == buf.value and o.name), c
+        assert o.stat_rows == L.yh_conv_stat_blocks(C.byref(d)) and o.bnr_rows == L.yh_conv_bnr_rows(C.byref(d)), c
+        refused += rc != 0
+        if rc == 0:
+            fams.add(o.family)
+    assert fams == set(range(12)) and 300 < refused < 1000, (fams, refused)
+    # valid but for its operands (the engine fills in a head gradient's address at run time): refused, and planned like the same
+    # layer with them.  A ring-kernel layer with a tail and a conv_pt_kernel data gradient with the fused reduction
+    for f, algo, want in (([0, 64, 80, 80, 80, 80, 1, 1, 0, 96, 1, 96, 96, 0, 0, 0, 96, 96, 0, 1, 0, 0, 0, 0, 0, 0], 3,
+                           (_lib.YH_CONV_FAM_V3, 2, 1, b"conv_v3_kernel<128, 128, 2, 2, 64, 2, 1, true>")),
+                          ([1, 64, 80, 80, 80, 80, 1, 1, 0, 64, 1, 128, 128, 0, 0, 0, 64, 64, 0, 0, 0, 0, 0, 0, 1, 0], 13,
+                           (_lib.YH_CONV_FAM_PT, 0, 0, b"conv_pt_kernel<128, 0, 3>"))):
+        c = dict(mod.case_of_key(f), algo=algo)
+        d, o, bare, ob = mod.make_desc(c), _lib.ConvInfo(), mod.make_desc(c), _lib.ConvInfo()
+        bare.seg[0].ptr = bare.w = bare.out0 = None
+        assert L.yh_conv_info(C.byref(d), C.byref(o)) == 0 and L.yh_conv_info(C.byref(bare), C.byref(ob)) != 0
+        assert (o.family, o.variant, o.tail, o.name) == want and o.stat_rows > 0
+        assert all(getattr(o, n) == getattr(ob, n) for n, _ in _lib.ConvInfo._fields_)
+
+
+CONV_PREFIX_GROUPS = {("conv6", "conv11", "dgrad"): 50, ("conv6", "conv11", "fwd"): 24, ("conv9", "conv11", "eval"): 6, ("conv9", "conv10", "eval"): 2}
+
+
+def test_conv_tune_keys_round_trip():
+    """TunerMixin._conv_tune_key rebuilds the conv keys of the shipped table from the descriptors they describe: 448 of the 530
+    exactly; the other 82 carry a version prefix the engine no longer asks for (entries from before conv_pt_kernel / conv_c80_kernel
+    joined their layers' candidates) beside a live twin under the new one.  The numbers are a property of tune_defaults.json"""
+    from yoloseries_amd.engine.tune import TunerMixin
+    mod = _conv_plan_table()
+    keys = {k: f for k, f, _ in mod.table_keys()}
+    assert len(keys) == 530
+    same, groups = 0, {}
+    for key, f in keys.items():
+        kind = key.split(":")[1]
+        got = TunerMixin._conv_tune_key(mod.make_desc(mod.case_of_key(f)), kind, False)
+        if got == key:
+            same += 1
+            continue
+        assert got.split(":")[1:] == key.split(":")[1:] and got in keys, (key, got)
+        g = (key.split(":")[0], got.split(":")[0], kind)
+        groups[g] = groups.get(g, 0) + 1
+    assert same == 448 and groups == CONV_PREFIX_GROUPS, (same, groups)
+
+
+def _conv_enum_desc(mod, f, kind, stats=False):
+    """the descriptor of a table key as the engine holds it when it enumerates candidates: the statistics pointer of a training
+    forward is attached only afterwards, for the timing"""
+    c = mod.case_of_key(f)
+    if kind == "fwd":
+        c["stats"] = int(stats)
+    return mod.make_desc(c)
+
+
+def test_conv_tuner_candidates():
+    """the (algo, tile_k, grid_cap) candidates the engine times per conv launch (TunerMixin._conv_candidates: the library's plan says
+    which requests it would honour) for every conv key of the shipped table, against tests/golden/conv_tune_candidates.json.  The record
+    was taken on the commit before this function existed, by running the enumeration loop _tune_conv had then — it asked
+    yh_conv_kernel_name per algo and matched substrings of the profiler spelling — over the same descriptors on the CPU; one line
+    per key, "<key> -> algo,tile_k,grid_cap;...", in the order of conv_plan_table.table_keys().  Every shipped choice is one of
+    its key's candidates; the list does not depend on the input address being known; a training forward gives the same list with
+    the statistics pointer attached, and its shipped choice the same statistics rows"""
+    import ctypes as C
+    import hashlib
+    import json
+    from yoloseries_amd._lib import lib
+    from yoloseries_amd.engine.tune import TunerMixin
+    mod, L = _conv_plan_table(), lib()
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "conv_tune_candidates.json")))
+    assert hashlib.sha256("\n".join(want).encode()).hexdigest() == "267a49d88aca1d279f2eaa3c7e6aa9f06a7f370cf1afc2ab057c5168c8725891"
+    got, total, nfwd = [], 0, 0
+    for key, f, (tile_k, grid_cap, algo) in mod.table_keys():
+        kind = key.split(":")[1]
+        d = _conv_enum_desc(mod, f, kind)
+        d.algo, d.tile_k, d.grid_cap = 3, 32, 24
+        cands = TunerMixin._conv_candidates(L, d, kind)
+        assert (d.algo, d.tile_k, d.grid_cap) == (3, 32, 24)          # the enumeration leaves the descriptor as it was
+        assert (algo, tile_k, grid_cap) in cands, (key, cands)
+        bare = _conv_enum_desc(mod, f, kind)
+        bare.seg[0].ptr = None          # (a head layer's data gradient: its input address arrives at run time)
+        assert TunerMixin._conv_candidates(L, bare, kind) == cands, key
+        if kind == "fwd":
+            ds = _conv_enum_desc(mod, f, kind, stats=True)
+            assert TunerMixin._conv_candidates(L, ds, kind) == cands, key
+            assert TunerMixin._conv_info(L, ds, algo, tile_k, grid_cap).stat_rows == TunerMixin._conv_info(L, d, algo, tile_k, grid_cap).stat_rows
+            nfwd += 1
+        total += len(cands)
+        got.append(f"{key} -> " + ";".join(f"{a},{tk},{cap}" for a, tk, cap in cands))
+    assert (len(got), total, nfwd) == (530, 3960, 118)
+    assert got == want, [(g, w) for g, w in zip(got, want) if g != w][:3]
+
+
+#   kind, key fields (conv_plan_table.case_of_key) | candidates
+CONV_CANDIDATE_ROWS = [
+    ("fwd", (0, 64, 320, 320, 320, 320, 3, 1, 1, 32, 1, 16, 16, 0, 0, 0, 32, 32, 0, 1, 0, 0, 0, 0, 0, 0), "1,0,0"),                                      # stem: nothing else
+    ("fwd", (0, 64, 80, 80, 80, 80, 1, 1, 0, 64, 1, 64, 64, 0, 0, 0, 64, 64, 0, 1, 0, 0, 0, 0, 0, 0), "1,0,0;1,0,1536;2,0,0;3,0,0;4,0,0"),               # v3, whole 64-channel blocks
+    ("fwd", (0, 64, 80, 80, 80, 80, 1, 1, 0, 96, 1, 96, 96, 0, 0, 0, 96, 96, 0, 1, 0, 0, 0, 0, 0, 0), "1,0,0;1,0,1024;2,0,0;2,32,0;3,0,0;3,32,0;4,0,0;4,32,0"),   # v3 with a tail
+    ("fwd", (0, 64, 20, 20, 20, 20, 3, 1, 1, 128, 1, 512, 512, 0, 0, 0, 128, 128, 0, 1, 0, 0, 0, 0, 0, 0), "1,0,0;1,32,0;2,0,0;3,0,0;4,0,0;5,0,0"),      # halo, both k-steps of v2
+    ("eval", (0, 32, 40, 40, 40, 40, 3, 1, 1, 640, 1, 640, 640, 0, 0, 0, 640, 640, 0, 0, 0, 1, 0, 1, 0, 0), "1,0,0;1,0,192;1,32,0;1,32,192;2,0,0;3,0,0;4,0,0;5,0,0;6,0,0"),   # halo160
+    ("dgrad", (1, 64, 320, 320, 160, 160, 3, 2, 1, 32, 1, 64, 64, 0, 0, 0, 32, 32, 0, 0, 0, 0, 0, 0, 1, 0), "1,0,0;1,0,2048;7,0,0"),                     # dg2
+    ("fwd", (0, 64, 160, 160, 160, 160, 3, 1, 1, 32, 1, 32, 32, 0, 0, 0, 32, 32, 0, 1, 0, 0, 0, 0, 0, 0), "1,0,0;1,0,2048;8,0,0"),                       # p3
+    ("eval", (0, 32, 320, 320, 320, 320, 3, 1, 1, 80, 1, 80, 80, 0, 0, 0, 80, 80, 0, 0, 1, 1, 0, 1, 0, 0), "1,0,0;1,0,1024;2,0,0;3,0,0;4,0,0;5,0,0;9,0,0"),      # h80
+    ("eval", (0, 32, 320, 320, 320, 320, 1, 1, 0, 80, 1, 80, 80, 0, 0, 0, 80, 80, 0, 0, 0, 1, 0, 1, 0, 0), "1,0,0;1,0,1024;2,0,0;3,0,0;4,0,0;10,0,0"),   # pw
+    ("eval", (0, 32, 320, 320, 640, 640, 3, 2, 1, 160, 1, 80, 80, 0, 0, 0, 160, 160, 0, 0, 0, 1, 0, 1, 0, 0), "1,0,0;1,0,512;2,0,0;3,0,0;4,0,0;12,0,0"), # c80
+    ("dgrad", (1, 64, 80, 80, 80, 80, 1, 1, 0, 64, 1, 128, 128, 0, 0, 0, 64, 64, 0, 0, 0, 0, 0, 0, 1, 0), "1,0,0;1,0,1536;2,0,0;3,0,0;4,0,0;13,0,0"),    # pt
+    ("fwd", (0, 64, 20, 20, 40, 40, 3, 2, 1, 256, 1, 256, 256, 0, 0, 0, 256, 256, 0, 1, 0, 0, 0, 0, 0, 0), "1,0,0;1,32,0;2,0,0;3,0,0;4,0,0;14,0,0"),     # the 256 x 256 tile
+]
+
+
+def test_conv_tuner_candidates_per_family(monkeypatch):
+    """one layer per kernel family: the candidate lists the tuner produced when it matched kernel names, and what the two switches
+    take out of them — YH_CONV_V3=0 everything but the register-staged kernel, flags.SKIP_ALGOS exactly the algos it names"""
+    from yoloseries_amd._lib import lib
+    from yoloseries_amd.engine import flags
+    from yoloseries_amd.engine.tune import TunerMixin
+    mod, L = _conv_plan_table(), lib()
+    monkeypatch.delenv("YH_CONV_V3", raising=False)
+    monkeypatch.setattr(flags, "SKIP_ALGOS", frozenset())
+    lists = []
+    for kind, f, want in CONV_CANDIDATE_ROWS:
+        cands = TunerMixin._conv_candidates(L, _conv_enum_desc(mod, f, kind), kind)
+        assert ";".join(f"{a},{tk},{cap}" for a, tk, cap in cands) == want, (kind, f)
+        lists.append(cands)
+    assert {a for cands in lists for a, _, _ in cands} == {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 13, 14}
+    monkeypatch.setattr(flags, "SKIP_ALGOS", frozenset(("3", "13", "14")))
+    for (kind, f, _), cands in zip(CONV_CANDIDATE_ROWS, lists):
+        assert TunerMixin._conv_candidates(L, _conv_enum_desc(mod, f, kind), kind) == [c for c in cands if c[0] not in (3, 13, 14)]
+    monkeypatch.setattr(flags, "SKIP_ALGOS", frozenset())
+    monkeypatch.setenv("YH_CONV_V3", "0")
+    for (kind, f, _), cands in zip(CONV_CANDIDATE_ROWS, lists):
+        assert TunerMixin._conv_candidates(L, _conv_enum_desc(mod, f, kind), kind) == [c for c in cands if c[0] == 1]
 
 
 def _wgrad_plan_table():

@@ -2,13 +2,11 @@
 """Kernel families of yh_conv_igemm side by side on representative layer shapes: register-staged conv_v2 (algo 1) against the
 LDS-DMA ring kernel conv_v3 with its 256x128 / 128x128 / 128x64 tiles (algo 2..4).
 usage: bench_algos.py [v5s|v5l|v5x1280] [fwd|dgrad|dgrad3|eval] [iters]"""
-import ctypes as C
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from yoloseries_amd import hipk
-from yoloseries_amd._lib import lib
 
 which = sys.argv[1] if len(sys.argv) > 1 else "v5s"
 mode = sys.argv[2] if len(sys.argv) > 2 else "fwd"
@@ -37,12 +35,6 @@ else:
 B = int(os.environ.get("BA_BATCH", B))                       # BA_BATCH / BA_ONLY: another batch size / only these shapes
 if os.environ.get("BA_ONLY"):
     shapes = [sh for sh in shapes if sh[0] in os.environ["BA_ONLY"].split(",")]
-
-
-def kname(d):
-    buf = C.create_string_buffer(96)
-    lib().yh_conv_kernel_name(C.byref(d), buf, 96)
-    return buf.value.decode()
 
 
 for name, H, Cin, Cout, k, s in shapes:
@@ -79,10 +71,7 @@ for name, H, Cin, Cout, k, s in shapes:
         d.algo = algo
         d.tile_k = int(os.environ.get("BA_TILE_K", 0)) if algo >= 7 else 0
         d.tile_n = int(os.environ.get("BA_TILE_N", 0)) if algo >= 7 else 0
-        kn = kname(d)
-        if (algo in (2, 3, 4) and "conv_v3" not in kn) or (algo == 5 and "conv_halo_kernel" not in kn) or (algo == 6 and "conv_halo160" not in kn) or \
-                (algo == 7 and "conv_dg2" not in kn) or (algo == 8 and "conv_p3" not in kn) or (algo == 9 and "conv_h80" not in kn) or (algo == 10 and "conv_pw" not in kn) or \
-                (algo == 13 and "conv_pt" not in kn) or (algo == 14 and "conv_v3_kernel<256, 256" not in kn):
+        if hipk.conv_kernel_name(d, honoured=True) is None:
             res.append("      -")
             continue
         for _ in range(2):

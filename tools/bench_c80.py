@@ -1,11 +1,10 @@
 #!/usr/bin/env python3
 """YOLOv5x stage-1 downsampling layer (ConvBnAct(80, 160, 3, 2) at 640 x 640, inference epilogue): conv_c80_kernel (algo 12) against
 every other eligible kernel family, isolated.   usage: bench_c80.py [batch] [iters]"""
-import sys, os, ctypes as C
+import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from yoloseries_amd import hipk
-from yoloseries_amd._lib import lib
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -21,12 +20,10 @@ scale = torch.rand(160, device=dev) + 0.5
 shift = torch.randn(160, device=dev)
 d = hipk.conv_desc([hipk.full(x)], hipk.YH_CONV_FWD, B, Ho, Ho, H, H, 3, stride, 1, wp, 160, hipk.full(out), scale=scale, shift=shift, act=hipk.YH_ACT_SILU)
 fl = 2.0 * B * Ho * Ho * 160 * 720
-buf = C.create_string_buffer(96)
 ref = None
 for algo, tk in ((1, 0), (2, 0), (2, 32), (3, 0), (3, 32), (4, 0), (4, 32), (12, 0)):
     d.algo, d.tile_k = algo, tk
-    lib().yh_conv_kernel_name(C.byref(d), buf, 96)
-    kn = buf.value.decode()
+    kn = hipk.conv_kernel_name(d)
     hipk.conv_launch(d)
     torch.cuda.synchronize()
     if ref is None:

@@ -4,14 +4,12 @@ the YOLOv5s / YOLOv5l training step at batch 64: forward with the BatchNorm part
 BatchNorm-backward reduction, one- and two-segment inputs.  Interleaved rounds in one process, median per kernel; GB/s on the
 algorithmic bytes (input once, output once, z once for the fused reduction).
 usage: bench_pt.py [v5s|v5l] [rounds] [iters]"""
-import ctypes as C
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from yoloseries_amd import hipk
-from yoloseries_amd._lib import lib
 
 which = sys.argv[1] if len(sys.argv) > 1 else "v5s"
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -30,12 +28,6 @@ else:
               ("s3_cba12", 40, (512, 0, 0), 512), ("s3_cba3", 40, (256, 256, 0), 512), ("h2_conv", 40, (512, 0, 0), 256), ("h2_cba12", 80, (256, 256, 1), 256)]
 if os.environ.get("BP_ONLY"):
     shapes = [sh for sh in shapes if sh[0] in os.environ["BP_ONLY"].split(",")]
-
-
-def kname(d):
-    buf = C.create_string_buffer(96)
-    lib().yh_conv_kernel_name(C.byref(d), buf, 96)
-    return buf.value.decode()
 
 
 def timeit(d):
@@ -80,8 +72,8 @@ for name, H, (C0, C1, ups0), N in shapes:
         cands = []
         for algo, tk in ((1, 0), (1, 32), (2, 0), (3, 0), (3, 32), (4, 0), (4, 32), (13, 0)):
             d.algo, d.tile_k, d.grid_cap = algo, tk, 0
-            kn = kname(d)
-            if (algo in (2, 3, 4) and "conv_v3" not in kn) or (algo == 13 and "conv_pt" not in kn):
+            kn = hipk.conv_kernel_name(d, honoured=True)
+            if kn is None:
                 continue
             cands.append((algo, tk, kn))
         times = {c: [] for c in cands}

@@ -1,8 +1,8 @@
 """Plan table of yh_conv_igemm: what the library decides for a descriptor, without a device.
 
-One line per descriptor:  key -> rc, kernel name, yh_conv_stat_blocks, yh_conv_bnr_rows  — obtained only through the three C-ABI
-calls (yh_conv_kernel_name, yh_conv_stat_blocks, yh_conv_bnr_rows).  Planning and naming are host code: the name path returns before
-any HIP call and dereferences no operand pointer, so the operands are fake 16-byte-aligned addresses and the table is the same on
+One line per descriptor:  key -> rc, kernel name, yh_conv_stat_blocks, yh_conv_bnr_rows  — obtained only through the C ABI
+(yh_conv_info, which answers what the three older queries answer).  Planning and naming are host code: the query makes
+no HIP call and dereferences no operand pointer, so the operands are fake 16-byte-aligned addresses and the table is the same on
 a machine without a GPU.  Two builds of the library plan alike exactly when their tables are byte-identical:
 
     YH_LIBRARY=/path/to/old/libyolohip.so python tools/conv_plan_table.py --all > old.txt
@@ -79,9 +79,10 @@ def make_desc(c):
 
 def answer(L, d):
     """'rc, kernel name, stat blocks, bnr rows' of one descriptor"""
-    buf = C.create_string_buffer(128)
-    rc = L.yh_conv_kernel_name(C.byref(d), buf, 128)
-    return f"{rc}, {buf.value.decode() if rc == 0 else '-'}, {L.yh_conv_stat_blocks(C.byref(d))}, {L.yh_conv_bnr_rows(C.byref(d))}"
+    from yoloseries_amd._lib import ConvInfo
+    o = ConvInfo()
+    rc = L.yh_conv_info(C.byref(d), C.byref(o))
+    return f"{rc}, {o.name.decode() if rc == 0 else '-'}, {o.stat_rows}, {o.bnr_rows}"
 
 
 def case_of_key(f):

@@ -7,7 +7,7 @@ import sys, os, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from yoloseries_amd import hipk
-from yoloseries_amd._lib import lib, LIB_PATH
+from yoloseries_amd._lib import LIB_PATH
 
 Cin = int(sys.argv[1]) if len(sys.argv) > 1 else 160
 H = int(sys.argv[2]) if len(sys.argv) > 2 else 160
@@ -28,11 +28,11 @@ if not hasattr(raw, "yh_halo_set_stamps"):
 else:
     raw.yh_halo_set_stamps.argtypes = [C.c_void_p]
     raw.yh_halo_set_stamps.restype = None
-buf = C.create_string_buffer(96)
 fl = 2.0 * B * H * H * N * 9 * Cin
 for algo in (6, 5, 3):
     d.algo = algo
-    if lib().yh_conv_kernel_name(C.byref(d), buf, 96):
+    kn = hipk.conv_kernel_name(d, honoured=True)
+    if kn is None:
         continue
     for _ in range(2):
         hipk.conv_launch(d)
@@ -43,7 +43,7 @@ for algo in (6, 5, 3):
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 5
-    print(f"algo {algo}: {buf.value.decode():44s} {ms:7.3f} ms  {fl / ms / 1e9:6.0f} TFLOP/s", flush=True)
+    print(f"algo {algo}: {kn:44s} {ms:7.3f} ms  {fl / ms / 1e9:6.0f} TFLOP/s", flush=True)
 if raw is None:
     sys.exit(0)
 d.algo = 6

@@ -61,6 +61,5 @@ for ki, key in enumerate(keys):
             vals = out[..., :N].reshape(-1, N)[rows[0]][cols[:8]].float().tolist()
             nbad.append((r, n, rows[:6].tolist(), int(rows.numel()), cols.tolist()[:20], [f"{v:.3g}" for v in vals]))
     bad_total += len(nbad)
-    name = C.create_string_buffer(96); L.yh_conv_kernel_name(C.byref(d), name, 96)
-    print(f"{name.value.decode():28s} {key.split(':')[1]:5s} {Ho}x{Wo} C{Ctot} N{N}: {len(nbad)} of {reps} launches wrong", nbad[:3], flush=True)
+    print(f"{hipk.conv_kernel_name(d):28s} {key.split(':')[1]:5s} {Ho}x{Wo} C{Ctot} N{N}: {len(nbad)} of {reps} launches wrong", nbad[:3], flush=True)
 print("launches with wrong elements:", bad_total)

@@ -88,7 +88,7 @@ def screen(reps=6, sub="", verbose=True, beside=False, deep=None, family=None, b
                 slab = torch.full((L.yh_conv_bnr_rows(C.byref(d)), 2, N), nan, device=dev)
                 d.bnr_part = slab.data_ptr()
             if r == 0:
-                nb = C.create_string_buffer(96); L.yh_conv_kernel_name(C.byref(d), nb, 96); name = nb.value.decode()
+                name = hipk.conv_kernel_name(d)
                 fams[name.split("<")[0]] = fams.get(name.split("<")[0], 0) + 1
                 nrep = max(reps, deep.get(name.split("<")[0], 0))
                 if family is not None and not name.startswith(family):          # family: only entries of this kernel (name prefix)

@@ -61,6 +61,21 @@ class WgradInfo(C.Structure):
 YH_WGRAD_IM2COL, YH_WGRAD_PATCH, YH_WGRAD_WAVE = 0, 1, 2
 
 
+class ConvInfo(C.Structure):
+    """yh_conv_plan_info: what yh_conv_igemm launches for a descriptor (yh_conv_info)"""
+    _fields_ = [("family", C.c_int32), ("variant", C.c_int32), ("tail", C.c_int32), ("stat_rows", C.c_int32), ("bnr_rows", C.c_int32),
+                ("reserved", C.c_int32), ("name", C.c_char * 96)]
+
+
+(YH_CONV_FAM_GENERIC, YH_CONV_FAM_V2, YH_CONV_FAM_V3, YH_CONV_FAM_HALO, YH_CONV_FAM_HALO160, YH_CONV_FAM_STEM, YH_CONV_FAM_DG2,
+ YH_CONV_FAM_P3, YH_CONV_FAM_H80, YH_CONV_FAM_PW, YH_CONV_FAM_C80, YH_CONV_FAM_PT) = range(12)
+# the kernel a request in yh_conv_desc.algo names, as (family, variant) of yh_conv_info: the library honours the request where its
+# plan says exactly that, and runs its default where the layer is not eligible (algos 0 / 1 ask for no sibling: always honoured)
+CONV_ALGO_FAMILY = {2: (YH_CONV_FAM_V3, 1), 3: (YH_CONV_FAM_V3, 2), 4: (YH_CONV_FAM_V3, 3), 14: (YH_CONV_FAM_V3, 4),
+                    5: (YH_CONV_FAM_HALO, 0), 6: (YH_CONV_FAM_HALO160, 0), 7: (YH_CONV_FAM_DG2, 0), 8: (YH_CONV_FAM_P3, 0),
+                    9: (YH_CONV_FAM_H80, 0), 10: (YH_CONV_FAM_PW, 0), 12: (YH_CONV_FAM_C80, 0), 13: (YH_CONV_FAM_PT, 0)}
+
+
 class V5LossDesc(C.Structure):
     _fields_ = [
         ("B", C.c_int32), ("maxbox", C.c_int32), ("num_class", C.c_int32), ("num_anchor", C.c_int32),
@@ -161,6 +176,7 @@ _SIGS = {
     "yh_conv_wgrad_info": (_i32, [C.POINTER(WgradDesc), C.POINTER(WgradInfo)]),
     "yh_conv_bnr_rows": (_i32, [C.POINTER(ConvDesc)]),
     "yh_conv_kernel_name": (_i32, [C.POINTER(ConvDesc), C.c_char_p, _i32]),
+    "yh_conv_info": (_i32, [C.POINTER(ConvDesc), C.POINTER(ConvInfo)]),
     "yh_bn_finalize": (_i32, [_vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp]),
     "yh_bn_fold": (_i32, [_vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp]),
     "yh_bn_frozen": (_i32, [_vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp]),

@@ -2585,7 +2585,7 @@ bool conv_desc_plannable(const yh_conv_desc* d) {
 }
 
 // ---- the plan: which instantiation runs for a descriptor, on what grid, writing how many partial-sum rows.  Made once per call
-// and read by the launcher, by yh_conv_kernel_name and by the two sizing entry points, so the four cannot drift apart.
+// and read by the launcher and by the queries (yh_conv_info and the three older ones, through conv_choose), so they cannot drift apart.
 enum ConvFamily { FAM_STEM, FAM_HALO160, FAM_HALO, FAM_V3, FAM_V2, FAM_GENERIC };
 struct ConvPlan {
     ConvFamily family;
@@ -2843,12 +2843,12 @@ int conv_launch(const ConvPlan& pl, hipStream_t st)
 // kernel (conv_p3.hip), 80-channel halo kernel (conv_h80.hip), pointwise kernels (conv_pw.hip, conv_pt.hip), 80 -> 160 kernel
 // (conv_c80.hip).  `who`: the entry points that hand the algo over (11 is unassigned: the launcher runs the default for it)
 enum { SIB_RUN = 1, SIB_STAT = 2, SIB_BNR = 4 };
-struct ConvSibling { int algo, who; int (*rows)(const yh_conv_desc*); int (*run)(const yh_conv_desc*, yh_stream, char*, int); };
+struct ConvSibling { int algo, who, family; int (*rows)(const yh_conv_desc*); int (*run)(const yh_conv_desc*, yh_stream, char*, int); };
 const ConvSibling CONV_SIBLINGS[] = {
-    {7, SIB_RUN | SIB_BNR, yh_dg2_rows, yh_dg2_run},           {8, SIB_RUN | SIB_STAT | SIB_BNR, yh_p3_rows, yh_p3_run},
-    {9, SIB_RUN, yh_h80_rows, yh_h80_run},                     {10, SIB_RUN, yh_pw_rows, yh_pw_run},
-    {11, SIB_RUN, nullptr, nullptr},                           {12, SIB_RUN, yh_c80_rows, yh_c80_run},
-    {13, SIB_RUN | SIB_STAT | SIB_BNR, yh_pt_rows, yh_pt_run},
+    {7, SIB_RUN | SIB_BNR, YH_CONV_FAM_DG2, yh_dg2_rows, yh_dg2_run},   {8, SIB_RUN | SIB_STAT | SIB_BNR, YH_CONV_FAM_P3, yh_p3_rows, yh_p3_run},
+    {9, SIB_RUN, YH_CONV_FAM_H80, yh_h80_rows, yh_h80_run},             {10, SIB_RUN, YH_CONV_FAM_PW, yh_pw_rows, yh_pw_run},
+    {11, SIB_RUN, 0, nullptr, nullptr},                                 {12, SIB_RUN, YH_CONV_FAM_C80, yh_c80_rows, yh_c80_run},
+    {13, SIB_RUN | SIB_STAT | SIB_BNR, YH_CONV_FAM_PT, yh_pt_rows, yh_pt_run},
 };
 // the sibling that takes the descriptor for entry point `who` (*rows: its grid rows), or nullptr.  Where the sibling of d->algo
 // declines, the library default (algo 0) plans instead: d then points to such a copy in *d0 — except for yh_conv_stat_blocks, which
@@ -2864,8 +2864,32 @@ const ConvSibling* conv_sibling(const yh_conv_desc*& d, yh_conv_desc* d0, int wh
     return nullptr;
 }
 
-// validates, plans and (name_out == nullptr) launches; with name_out only the instantiation's name is produced
-int conv_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len)
+// what entry point `who` (SIB_*) is answered from: the sibling that takes d (`rows`: its grid rows), else the plan `pl` of `d`,
+// which then is the caller's descriptor or the algo-0 copy of it in `d0` (conv_sibling).  The one path behind the launcher and
+// all four queries.  d must be plannable.
+struct ConvChoice { const ConvSibling* sib; int rows; const yh_conv_desc* d; yh_conv_desc d0; ConvPlan pl; };
+void conv_choose(const yh_conv_desc* d, int who, ConvChoice* c)
+{
+    c->d = d;
+    c->sib = conv_sibling(c->d, &c->d0, who, &c->rows);
+    if (!c->sib) conv_plan(c->d, &c->pl);
+}
+// rows of the statistics slab (SIB_STAT) / of the fused-reduction slab (SIB_BNR)
+int conv_rows(const yh_conv_desc* d, int who)
+{
+    ConvChoice c;
+    conv_choose(d, who, &c);
+    return c.sib ? c.rows : (who == SIB_STAT ? c.pl.stat_rows : c.pl.bnr_rows);
+}
+// yh_conv_bnr_rows' own preconditions, asked before it plans
+bool conv_bnr_possible(const yh_conv_desc* d)
+{
+    if (d->mode != YH_CONV_DGRAD || d->nseg != 1 || d->seg[0].C % 8 || d->seg[0].ups || d->N % 8) return false;
+    return !(conv_generic_na(d) || d->stats || (conv_dbg_mask() & 16));
+}
+
+// the argument checks of yh_conv_igemm that need no plan (a descriptor that passes is plannable)
+int conv_check_args(const yh_conv_desc* d)
 {
     YH_CHECK_ARG(d != nullptr, "yh_conv_igemm: null desc");
     YH_CHECK_ARG(d->nseg == 1 || d->nseg == 2, "yh_conv_igemm: nseg must be 1 or 2 (got %d)", d->nseg);
@@ -2894,12 +2918,11 @@ int conv_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_l
                      "yh_conv_igemm: dgrad geometry mismatch Ho=%d Hi=%d k=%d s=%d p=%d", d->Ho, d->Hi, d->KH, d->stride, d->pad);
     }
     YH_CHECK_ARG((long)d->B * d->Ho * d->Wo < (1L << 31) - BM, "yh_conv_igemm: too many output pixels");
-    yh_conv_desc d0;
-    int rows;
-    if (const ConvSibling* sib = conv_sibling(d, &d0, SIB_RUN, &rows)) return sib->run(d, stream, name_out, name_len);
-
-    ConvPlan pl;
-    conv_plan(d, &pl);          // (plannable: checked above)
+    return YH_OK;
+}
+// ... and those that read the plan
+int conv_check_plan(const yh_conv_desc* d, const ConvPlan& pl)
+{
     YH_CHECK_ARG(pl.gy * pl.bn <= d->Npad, "yh_conv_igemm: Npad too small for tile");
     if (d->bnr_part && pl.family != FAM_STEM) {
         YH_CHECK_ARG((pl.k.v2 || pl.family == FAM_V3) && !conv_generic_na(d) && !d->stats && d->mode == YH_CONV_DGRAD,
@@ -2908,43 +2931,71 @@ int conv_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_l
                      "yh_conv_igemm: bad fused-reduction operands");
     }
     if (pl.family == FAM_HALO160 || pl.family == FAM_HALO) YH_CHECK_ARG(pl.k.v2 && !pl.k.cls, "yh_conv_igemm: the halo kernel needs the buffer-load path");
-    if (name_out) { conv_plan_name(pl, name_out, name_len); return YH_OK; }
-    return conv_launch(pl, (hipStream_t)stream);
+    return YH_OK;
+}
+int conv_public_family(ConvFamily f)
+{
+    static const int pub[] = {YH_CONV_FAM_STEM, YH_CONV_FAM_HALO160, YH_CONV_FAM_HALO, YH_CONV_FAM_V3, YH_CONV_FAM_V2, YH_CONV_FAM_GENERIC};
+    return pub[f];
 }
 }  // namespace
 
-extern "C" int yh_conv_igemm(const yh_conv_desc* d, yh_stream stream) { return conv_run(d, stream, nullptr, 0); }
+extern "C" int yh_conv_igemm(const yh_conv_desc* d, yh_stream stream)
+{
+    if (const int rc = conv_check_args(d)) return rc;
+    ConvChoice c;
+    conv_choose(d, SIB_RUN, &c);
+    if (c.sib) return c.sib->run(c.d, stream, nullptr, 0);
+    if (const int rc = conv_check_plan(c.d, c.pl)) return rc;
+    return conv_launch(c.pl, (hipStream_t)stream);
+}
+
+/* what yh_conv_igemm(d) will launch (include/yolohip.h): the rc of the launch's checks; `out` is filled from the dims alone
+ * whenever the descriptor is plannable.  (A sibling's name comes from its launcher, which checks its fused-reduction operands
+ * first: without them the name stays empty.) */
+extern "C" int yh_conv_info(const yh_conv_desc* d, yh_conv_plan_info* out)
+{
+    YH_CHECK_ARG(out != nullptr, "yh_conv_info: null out");
+    memset(out, 0, sizeof(*out));
+    int rc = conv_check_args(d);
+    if (!conv_desc_plannable(d)) return rc;
+    ConvChoice c;
+    conv_choose(d, SIB_RUN, &c);
+    if (c.sib) {
+        out->family = c.sib->family;
+        const int rc_name = c.sib->run(c.d, nullptr, out->name, (int)sizeof(out->name));
+        if (rc == YH_OK) rc = rc_name;
+    } else {
+        out->family = conv_public_family(c.pl.family);
+        out->variant = c.pl.v3;
+        out->tail = c.pl.tl ? 1 : 0;
+        conv_plan_name(c.pl, out->name, (int)sizeof(out->name));
+        if (rc == YH_OK) rc = conv_check_plan(c.d, c.pl);
+    }
+    out->stat_rows = conv_rows(d, SIB_STAT);
+    out->bnr_rows = conv_bnr_possible(d) ? conv_rows(d, SIB_BNR) : 0;
+    return rc;
+}
 
 /* name of the kernel instantiation yh_conv_igemm launches for this descriptor, as profilers print it */
 extern "C" int yh_conv_kernel_name(const yh_conv_desc* d, char* buf, int buflen)
 {
     YH_CHECK_ARG(buf && buflen >= 64, "yh_conv_kernel_name: buffer too small");
-    return conv_run(d, nullptr, buf, buflen);
+    yh_conv_plan_info o;
+    const int rc = yh_conv_info(d, &o);
+    if (rc == YH_OK) snprintf(buf, buflen, "%s", o.name);
+    return rc;
 }
 
 /* rows of the BatchNorm partial-sum slab (d->stats) the launch for this descriptor writes */
-extern "C" int yh_conv_stat_blocks(const yh_conv_desc* d)
-{
-    if (!conv_desc_plannable(d)) return 0;
-    yh_conv_desc d0;
-    int rows;
-    if (conv_sibling(d, &d0, SIB_STAT, &rows)) return rows;
-    ConvPlan pl;
-    return conv_plan(d, &pl) ? pl.stat_rows : 0;
-}
+extern "C" int yh_conv_stat_blocks(const yh_conv_desc* d) { return conv_desc_plannable(d) ? conv_rows(d, SIB_STAT) : 0; }
 
 /* rows of the partial-sum slab a data-gradient launch with the fused BatchNorm-backward reduction (bnr_*) writes:
  * [rows][2][N] floats (sum dz | sum dz*z), consumed by yh_bn_bwd_finalize(part, rows, ...).  0: this descriptor
  * cannot take the fused path (the caller keeps the separate yh_bn_silu_bwd_reduce pass). */
 extern "C" int yh_conv_bnr_rows(const yh_conv_desc* d)
 {
-    if (!conv_desc_plannable(d) || d->mode != YH_CONV_DGRAD || d->nseg != 1 || d->seg[0].C % 8 || d->seg[0].ups || d->N % 8) return 0;
-    if (conv_generic_na(d) || d->stats || (conv_dbg_mask() & 16)) return 0;
-    yh_conv_desc d0;
-    int rows;
-    if (conv_sibling(d, &d0, SIB_BNR, &rows)) return rows;
-    ConvPlan pl;
-    return conv_plan(d, &pl) ? pl.bnr_rows : 0;
+    return conv_desc_plannable(d) && conv_bnr_possible(d) ? conv_rows(d, SIB_BNR) : 0;
 }
 
 /* diagnostics: a device buffer of grid x 8 x 8 uint64 that receives cycle sums of every workgroup's 2nd tile in conv_halo160_kernel (NULL: off) */

@@ -489,7 +489,7 @@ bool pt_plan(const yh_conv_desc* d, PtPlan* pl)
     memset(&k, 0, sizeof(k));
     for (int s = 0; s < d->nseg; ++s) {
         const yh_seg& g = d->seg[s];
-        if (!g.ptr || g.ld % 8 || g.ld < g.C || (g.ups != 0 && g.ups != 1)) return false;
+        if (g.ld % 8 || g.ld < g.C || (g.ups != 0 && g.ups != 1)) return false;          // (a null pointer is the launcher's to refuse: the plan reads dims)
         if (g.ups && (d->Hi % 2 || d->Wi % 2)) return false;
         const unsigned long npix = (unsigned long)d->B * (d->Hi >> g.ups) * (d->Wi >> g.ups);
         const unsigned long bytes = ((npix - 1) * g.ld + g.C) * 2;

@@ -40,17 +40,28 @@ class BackwardMixin:
                     ((op.N <= 32 and Kseg0 <= 256) or (op.N > 32 and 128 < Kseg0 <= 256)) and
                     (_flags.FUSE_STEM_BWD >= 2 or (self.wg_ws is None and self._stem_patch_ok(op))))
 
-    def _stem_patch_ok(self, op):
-        """does the patch form of the weight gradient (conv_wgpf_kernel) take this layer with the fused BatchNorm backward?"""
+    def _wgrad_desc(self, op, sg, coff_k, gy, ldg, N, bn=None, dw=None):
+        """yh_wgrad_desc of input segment sg of op.  bn = (ws, gamma, coef) pointers: gy is the gradient of the activation and the
+        BatchNorm backward apply runs inside the launch (the fused stem)"""
         wd = WgradDesc()
-        wd.gy, wd.ldg, wd.N = op.y.t.data_ptr(), op.N, op.N
-        wd.bn_z, wd.bn_ldz = op.y.t.data_ptr(), op.y.C
-        wd.bn_ws = wd.bn_gamma = wd.bn_coef = op.y.t.data_ptr()          # placeholders: eligibility only looks at null / alignment
-        wd.seg = hipk.make_seg(op.segs[0].sl())
-        wd.coff_k, wd.Ctot = 0, op.Ctot
+        wd.gy, wd.ldg, wd.N = gy, ldg, N
+        if bn:
+            wd.bn_z, wd.bn_ldz = op.y.t.data_ptr(), op.y.C
+            wd.bn_ws, wd.bn_gamma, wd.bn_coef = bn
+        wd.seg = hipk.make_seg(sg.sl())
+        wd.coff_k, wd.Ctot = coff_k, op.Ctot
         wd.B, wd.Ho, wd.Wo, wd.Hi, wd.Wi = self.B, op.Ho, op.Wo, op.Hi, op.Wi
         wd.KH = wd.KW = op.k
         wd.stride, wd.pad = op.stride, op.pad
+        wd.dw = dw
+        if self.wg_ws is not None:
+            wd.partial, wd.partial_bytes = self.wg_ws.data_ptr(), self.wg_ws.numel() * 4
+        return wd
+
+    def _stem_patch_ok(self, op):
+        """does the patch form of the weight gradient (conv_wgpf_kernel) take this layer with the fused BatchNorm backward?"""
+        z = op.y.t.data_ptr()          # placeholder operands: eligibility only looks at null / alignment
+        wd = self._wgrad_desc(op, op.segs[0], 0, z, op.N, op.N, bn=(z, z, z))
         wd.tile_k = 40
         return bool(self.L.yh_conv_wgrad_patch_ok(C.byref(wd)))
 
@@ -261,28 +272,15 @@ class BackwardMixin:
             # critical chain (it waits for the finalize behind the last data gradient): it stays on the main stream, beside the side
             # stream's last weight gradient instead of behind it
             on_main = op.kind == 'cba' and fused_stem
-            def wgrad_desc_for(sg, coff_k):
-                wd = WgradDesc()
-                wd.gy = gys.data_ptr() if op.kind == 'cba' else 0
-                wd.ldg, wd.N = gy_ld, gyN
-                if op.kind == 'cba' and fused_stem:
-                    ga_, ws_, bn_, coef_ = st['fused_bwd']
-                    wd.gy, wd.ldg = ga_.ptr(), ga_.ld
-                    wd.bn_z, wd.bn_ldz = op.y.t.data_ptr(), op.y.C
-                    wd.bn_ws, wd.bn_gamma, wd.bn_coef = ws_.data_ptr(), bn_.weight.data_ptr(), coef_.data_ptr()
-                wd.seg = hipk.make_seg(sg.sl())
-                wd.coff_k, wd.Ctot = coff_k, op.Ctot
-                wd.B, wd.Ho, wd.Wo, wd.Hi, wd.Wi = B, op.Ho, op.Wo, op.Hi, op.Wi
-                wd.KH = wd.KW = op.k
-                wd.stride, wd.pad = op.stride, op.pad
-                wd.dw = gdw
-                if self.wg_ws is not None:
-                    wd.partial, wd.partial_bytes = self.wg_ws.data_ptr(), self.wg_ws.numel() * 4
-                return wd
+            if on_main:
+                ga_, ws_, bn_, coef_ = st['fused_bwd']
+                wg_args = (ga_.ptr(), ga_.ld, gyN, (ws_.data_ptr(), bn_.weight.data_ptr(), coef_.data_ptr()), gdw)
+            else:
+                wg_args = (gys.data_ptr() if op.kind == 'cba' else 0, gy_ld, gyN, None, gdw)
             coff_k = 0
             launches = []
             for si, sg in enumerate(op.segs):
-                wd = wgrad_desc_for(sg, coff_k)
+                wd = self._wgrad_desc(op, sg, coff_k, *wg_args)
                 ntile = L.yh_conv_wgrad_tiles(gyN, op.k * op.k * sg.C)
                 kcols = op.k * op.k * (12 if op.focus else sg.C)
                 nbytes_x = 2.0 * B * (op.Hi >> sg.ups) * (op.Wi >> sg.ups) * sg.C
@@ -336,22 +334,22 @@ class BackwardMixin:
                     d.out0, d.ld0, d.accumulate = gl.ptr(), gl.ld, acc
                     self._keep.append(d)
                     key = (sg.buf.name, sg.coff, sg.C)
-                    if fuse_ok and key in producer_of and last_writer(key) and (acc == 0 or fuse_acc):
-                        rows = L.yh_conv_bnr_rows(C.byref(d))
-                        if rows > 0:
-                            po, ppi, pc0 = producer_of[key]
-                            d.bnr_z, d.bnr_ldz = po.y.t.data_ptr() + 2 * pc0, po.y.C
-                            d.bnr_ws, d.bnr_C = self.op_state[po.name]['ws'][ppi].data_ptr(), sg.C
+                    def bnr_slab(po, ppi):
+                        """size the fused reduction's slab for the grid d has now; its rows (0: d cannot take the fused reduction)"""
+                        rows = self._conv_info(L, d).bnr_rows
+                        if rows != self.bnr_fused.get((po.name, ppi), (None, 0))[1]:
                             slab = torch.zeros(rows * 2 * sg.C, dtype=torch.float32, device=self.dev)
                             d.bnr_part = slab.data_ptr()
                             self.bnr_fused[(po.name, ppi)] = (slab, rows)
+                        return rows
+                    if fuse_ok and key in producer_of and last_writer(key) and (acc == 0 or fuse_acc):
+                        po, ppi, pc0 = producer_of[key]
+                        if bnr_slab(po, ppi) > 0:
+                            d.bnr_z, d.bnr_ldz = po.y.t.data_ptr() + 2 * pc0, po.y.C
+                            d.bnr_ws, d.bnr_C = self.op_state[po.name]['ws'][ppi].data_ptr(), sg.C
                     self._tune_conv(d, 'dgrad', op.name)
-                    if d.bnr_part and L.yh_conv_bnr_rows(C.byref(d)) != self.bnr_fused[(po.name, ppi)][1]:
-                        # the tuned block cap changed the grid: size the slab for it
-                        rows = L.yh_conv_bnr_rows(C.byref(d))
-                        slab = torch.zeros(rows * 2 * sg.C, dtype=torch.float32, device=self.dev)
-                        d.bnr_part = slab.data_ptr()
-                        self.bnr_fused[(po.name, ppi)] = (slab, rows)
+                    if d.bnr_part:
+                        bnr_slab(po, ppi)          # the tuned block cap may have changed the grid
                     cmds.append(('dgrad', op, d, (self._kernel_name(d), 2.0 * M * op.N * op.k * op.k * sg.C, self._conv_bytes(d))))
         if self.wg_ws is not None:       # the shared workspace: what the largest launch of the program needs
             need = max([int(L.yh_conv_wgrad_ws_bytes(C.byref(wd))) for wd in wg_descs] + [16])

@@ -190,11 +190,13 @@ class ForwardMixin:
             d.act = YH_ACT_NONE
             d.out0, d.ld0, d.nsplit = op.y.t.data_ptr(), op.y.C, op.N
             self._tune_conv(d, 'fwd', op.name, stats_ok=True)
-            nblk = L.yh_conv_stat_blocks(C.byref(d))
+            d.stats = 1          # (the plan only reads whether statistics are collected; the slab is sized from its rows)
+            info = self._conv_info(L, d)
+            nblk = info.stat_rows
             st['stats'] = torch.zeros(nblk, 2, op.Npad, dtype=torch.float32, device=self.dev)
             d.stats = st['stats'].data_ptr()
             st['desc_train'] = d
-            self.cmd_train.append((L.yh_conv_igemm, (d,), op.name, self._fam_conv(op, d)))
+            self.cmd_train.append((L.yh_conv_igemm, (d,), op.name, self._fam_conv(op, d, info)))
             st['ws'] = []
             c0 = 0
             merged = _flags.MERGE_PARTS and 2 <= len(op.parts) <= YH_BN_MAX_PARTS and op.res is None
@@ -237,9 +239,10 @@ class ForwardMixin:
         out = 2.0 * d.B * d.Ho * d.Wo * d.N
         return rd + out * (2.0 if d.accumulate else 1.0) + (out * min(1.0, d.nsplit / max(d.N, 1)) if d.res else 0.0) + (out if d.bnr_part else 0.0)
 
-    def _fam_conv(self, op, d):
+    def _fam_conv(self, op, d, info=None):
         M = self.B * op.Ho * op.Wo
-        return (self._kernel_name(d), 2.0 * M * op.N * op.k * op.k * (12 if op.focus else op.Ctot), self._conv_bytes(d))
+        name = info.name.decode() if info else self._kernel_name(d)
+        return (name, 2.0 * M * op.N * op.k * op.k * (12 if op.focus else op.Ctot), self._conv_bytes(d))
 
     def _compile(self, cmds):
         cc = CompiledCmds(self.L, len(cmds))

@@ -6,7 +6,7 @@ import os
 
 import torch
 
-from .._lib import YH_CONV_DGRAD, YH_WGRAD_PATCH, YH_WGRAD_WAVE, WgradInfo, check
+from .._lib import CONV_ALGO_FAMILY, YH_CONV_DGRAD, YH_WGRAD_PATCH, YH_WGRAD_WAVE, ConvInfo, WgradInfo, check
 from . import flags as _flags
 
 # the table shipped with the package lives beside the package modules
@@ -110,61 +110,24 @@ class TunerMixin:
         only the number of BatchNorm partial-sum rows follows the grid."""
         if os.environ.get("YH_CONV_TUNE", "1") == "0":
             return
-        small3 = d.KH == 3 and d.stride == 1 and d.nseg == 1 and d.seg[0].C <= 128 and d.N <= 128 and kind != 'eval'
-        c80 = kind == 'eval' and d.KH == 3 and d.nseg == 1 and d.seg[0].C == 80 and d.N == 160
-        h160 = kind == 'eval' and d.KH == 3 and d.stride == 1 and d.nseg == 1 and d.N % 160 == 0 and d.seg[0].C >= 64 and d.seg[0].C % 32 == 0
-        ctot = d.seg[0].C + (d.seg[1].C if d.nseg > 1 else 0)
-        pt = kind != 'eval' and d.KH == 1 and d.stride == 1 and ctot in (128, 256, 512) and (d.nseg == 1 or d.seg[0].C == d.seg[1].C)
-        pte = kind == 'eval' and d.KH == 1 and d.stride == 1 and d.nseg == 1 and ctot == 320 and d.nsplit >= d.N     # conv_pt_kernel's inference form
-        key = f"{KEY_CONV_S2D if d.mode == YH_CONV_DGRAD and d.stride == 2 else (KEY_CONV_P3 if small3 else ((KEY_CONV_C80 if c80 else (KEY_CONV_H160 if h160 else (KEY_CONV_PT if pte else KEY_CONV_EVAL))) if kind == 'eval' else (KEY_CONV_PT if pt else KEY_CONV)))}:{kind}:" + ",".join(str(int(v)) for v in (
-            d.mode, d.B, d.Ho, d.Wo, d.Hi, d.Wi, d.KH, d.stride, d.pad, d.N, d.nseg, d.seg[0].C, d.seg[0].ld, d.seg[0].ups,
-            d.seg[1].C if d.nseg > 1 else 0, d.seg[1].ups if d.nseg > 1 else 0, d.ld0, d.nsplit, d.accumulate, int(bool(d.stats or stats_ok)),
-            int(bool(d.res)), d.act, int(bool(d.bias)), int(bool(d.scale)), int(bool(d.bnr_part)), 0))
+        key = self._conv_tune_key(d, kind, stats_ok)
         cache = _tune_cache()
         if key in cache:
             d.tile_k, d.grid_cap, d.algo = (int(v) for v in cache[key])
             return
         L = self.L
-        saved = (d.seg[0].ptr, d.stats)
+        cands = self._conv_candidates(L, d, kind)
+        # scratch operands big enough for every grid tried below (the head gradient pointer is filled in at run time)
+        infos = [self._conv_info(L, d, *c) for c in cands]
+        rows_max = max([1] + [o.stat_rows for o in infos])
+        bnr_max = max([1] + [o.bnr_rows for o in infos]) if d.bnr_part else 1
+        saved = (d.seg[0].ptr, d.stats, d.bnr_part)
         if not d.seg[0].ptr:
             d.seg[0].ptr = self.gy_scratch.data_ptr()
-        # candidates: (algo, tile_k, grid_cap)
-        d.tile_k = d.grid_cap = 0
-        d.algo = 1
-        base = L.yh_conv_stat_blocks(C.byref(d))
-        cands = []
-        tks = (0, 32) if all(d.seg[i].C % 64 == 0 for i in range(d.nseg)) and d.N > 64 else (0,)
-        for tk in tks:
-            for cap in (0, 2 * base):
-                d.tile_k, d.grid_cap = tk, cap
-                if cap and L.yh_conv_stat_blocks(C.byref(d)) == base:
-                    continue                       # fewer tiles than blocks: the cap changes nothing
-                cands.append((1, tk, cap))
-        d.tile_k = d.grid_cap = 0
-        if os.environ.get("YH_CONV_V3", "1") != "0":
-            for algo in (2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 13, 14):
-                if str(algo) in _flags.SKIP_ALGOS:
-                    continue
-                d.algo = algo
-                kn = self._kernel_name(d)
-                if ("conv_v3" in kn and algo < 5) or ("conv_halo_kernel" in kn and algo == 5) or ("conv_halo160" in kn and algo == 6) or \
-                        ("conv_dg2" in kn and algo == 7) or ("conv_p3" in kn and algo == 8) or ("conv_h80" in kn and algo == 9) or ("conv_pw" in kn and algo == 10) or ("conv_c80" in kn and algo == 12) or \
-                        ("conv_pt" in kn and algo == 13) or ("conv_v3_kernel<256, 256" in kn and algo == 14):
-                    cands.append((algo, 0, 0))
-                    if algo < 5 and kn.endswith(", true>") and all(d.seg[i].C % 32 == 0 for i in range(d.nseg)):
-                        cands.append((algo, 32, 0))    # ragged last channel block: 32-channel steps instead of 64 + tail
-        rows_max, bnr_max = 1, 1
-        for algo, tk, cap in cands:
-            d.algo, d.tile_k, d.grid_cap = algo, tk, cap
-            rows_max = max(rows_max, L.yh_conv_stat_blocks(C.byref(d)))
-            if d.bnr_part:
-                bnr_max = max(bnr_max, L.yh_conv_bnr_rows(C.byref(d)))
-        tmp_stats = None
         if stats_ok:
             tmp_stats = torch.zeros(rows_max + 8, 2, d.Npad, dtype=torch.float32, device=self.dev)
             d.stats = tmp_stats.data_ptr()
-        saved_part, tmp_part = d.bnr_part, None
-        if d.bnr_part:                   # a slab big enough for every grid tried below
+        if d.bnr_part:
             tmp_part = torch.zeros((bnr_max + 8) * 2 * d.N, dtype=torch.float32, device=self.dev)
             d.bnr_part = tmp_part.data_ptr()
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -182,20 +145,71 @@ class TunerMixin:
             if best_ms is None or ms < best_ms * (0.97 if _flags.TUNE_ITERS < 8 else 0.99):   # keep the earlier candidate unless clearly better
                 best, best_ms = (tk, cap, algo), ms
         d.tile_k, d.grid_cap, d.algo = best
-        d.seg[0].ptr, d.stats = saved
-        d.bnr_part = saved_part
+        d.seg[0].ptr, d.stats, d.bnr_part = saved
         cache[key] = [int(best[0]), int(best[1]), int(best[2])]
+
+    @staticmethod
+    def _conv_info(L, d, algo=None, tile_k=None, grid_cap=None):
+        """the library's plan for this descriptor (yh_conv_info), optionally with other launch parameters asked; no device needed"""
+        o, saved = ConvInfo(), (d.algo, d.tile_k, d.grid_cap)
+        d.algo, d.tile_k, d.grid_cap = (s if v is None else v for v, s in zip((algo, tile_k, grid_cap), saved))
+        L.yh_conv_info(C.byref(d), C.byref(o))             # (the rc speaks of operands: the callers want the plan)
+        d.algo, d.tile_k, d.grid_cap = saved
+        return o
+
+    @staticmethod
+    def _conv_tune_key(d, kind, stats_ok):
+        """key of this launch in the tuning tables: a version prefix by the candidates the layer has (TUNE_KEY_VERSIONS), the kind
+        of launch, and every descriptor field a timing depends on"""
+        one = d.nseg == 1
+        c0 = d.seg[0].C
+        ctot = c0 + (d.seg[1].C if d.nseg > 1 else 0)
+        pointwise = d.KH == 1 and d.stride == 1
+        if d.mode == YH_CONV_DGRAD and d.stride == 2:
+            prefix = KEY_CONV_S2D
+        elif kind != 'eval':
+            small3 = d.KH == 3 and d.stride == 1 and one and c0 <= 128 and d.N <= 128
+            pt = pointwise and ctot in (128, 256, 512) and (one or c0 == d.seg[1].C)
+            prefix = KEY_CONV_P3 if small3 else (KEY_CONV_PT if pt else KEY_CONV)
+        else:
+            c80 = d.KH == 3 and one and c0 == 80 and d.N == 160
+            h160 = d.KH == 3 and d.stride == 1 and one and d.N % 160 == 0 and c0 >= 64 and c0 % 32 == 0
+            pte = pointwise and one and ctot == 320 and d.nsplit >= d.N     # conv_pt_kernel's inference form
+            prefix = KEY_CONV_C80 if c80 else (KEY_CONV_H160 if h160 else (KEY_CONV_PT if pte else KEY_CONV_EVAL))
+        return f"{prefix}:{kind}:" + ",".join(str(int(v)) for v in (
+            d.mode, d.B, d.Ho, d.Wo, d.Hi, d.Wi, d.KH, d.stride, d.pad, d.N, d.nseg, d.seg[0].C, d.seg[0].ld, d.seg[0].ups,
+            d.seg[1].C if d.nseg > 1 else 0, d.seg[1].ups if d.nseg > 1 else 0, d.ld0, d.nsplit, d.accumulate, int(bool(d.stats or stats_ok)),
+            int(bool(d.res)), d.act, int(bool(d.bias)), int(bool(d.scale)), int(bool(d.bnr_part)), 0))
+
+    @staticmethod
+    def _conv_candidates(L, d, kind):
+        """[(algo, tile_k, grid_cap)] _tune_conv times for this descriptor, in that order.  Which requests the library would honour
+        is read from its plan (CONV_ALGO_FAMILY); which of them are worth timing is decided here.  Needs no device, leaves d alone."""
+        info = lambda algo, tk=0, cap=0: TunerMixin._conv_info(L, d, algo, tk, cap)     # noqa: E731
+        whole = lambda n: all(d.seg[i].C % n == 0 for i in range(d.nseg))               # noqa: E731
+        base = info(1).stat_rows
+        cands = []
+        for tk in ((0, 32) if whole(64) and d.N > 64 else (0,)):
+            for cap in (0, 2 * base):
+                if cap and info(1, tk, cap).stat_rows == base:
+                    continue                       # fewer tiles than blocks: the cap changes nothing
+                cands.append((1, tk, cap))
+        if os.environ.get("YH_CONV_V3", "1") == "0":
+            return cands
+        for algo in (2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 13, 14):
+            if str(algo) in _flags.SKIP_ALGOS:
+                continue
+            o = info(algo)
+            if (o.family, o.variant) != CONV_ALGO_FAMILY[algo]:
+                continue                           # not eligible: the library would run its default
+            cands.append((algo, 0, 0))
+            if algo < 5 and o.tail and whole(32):
+                cands.append((algo, 32, 0))        # ragged last channel block: 32-channel steps instead of 64 + tail
+        return cands
 
     def _kernel_name(self, d):
         """instantiation yh_conv_igemm launches for descriptor d, spelled as rocprofv3 prints it"""
-        buf = C.create_string_buffer(96)
-        saved = d.seg[0].ptr
-        if not saved:                      # head gradient pointer is filled in at run time
-            d.seg[0].ptr = self.gy_scratch.data_ptr()
-        rc = self.L.yh_conv_kernel_name(C.byref(d), buf, 96)
-        d.seg[0].ptr = saved
-        check(rc, "yh_conv_kernel_name")
-        return buf.value.decode()
+        return self._conv_info(self.L, d).name.decode()
 
     def _tune_wgrad_splits(self, wd, M, ntile, op):
         """Split-M factor (and, for the wide 64-row tilings, the pixels per k-step) of one weight-gradient launch.  The best

@@ -95,6 +95,16 @@ def conv_stat_blocks(d: ConvDesc) -> int:
     return lib().yh_conv_stat_blocks(C.byref(d))
 
 
+def conv_kernel_name(d: ConvDesc, honoured=False):
+    """instantiation yh_conv_igemm launches for d, profiler spelling (yh_conv_info: no device needed).  honoured=True: None where
+    the layer is not eligible for the kernel d.algo asks for (the library would run its default instead)"""
+    o = _lib.ConvInfo()
+    lib().yh_conv_info(C.byref(d), C.byref(o))             # (the rc speaks of operands: the callers want the plan)
+    if honoured and _lib.CONV_ALGO_FAMILY.get(d.algo, (o.family, o.variant)) != (o.family, o.variant):
+        return None
+    return o.name.decode()
+
+
 def conv_launch(d: ConvDesc):
     check(lib().yh_conv_igemm(C.byref(d), _st()), "yh_conv_igemm")
 
