@@ -551,6 +551,26 @@ size_t yh_nms_ws_bytes(int B, int cap);
 int yh_nms_batched(const float* cand, const int32_t* ncand, int B, int cap,
                    float iou_thr, int class_aware, int thr_inclusive, int max_keep, int merge_filter,
                    float* out, int32_t* nkeep, int32_t* keep_idx, void* ws, yh_stream stream);
+/* Validation metric on the device (yoloseries_amd/csrc/metric.hip lists the operation order): the NMS table of a batch and its
+ * ground truth, both in the letterboxed frame, to the per-detection match table of utils/mAP.py — the un-letterbox of
+ * val_yolov5.py (preds_postprocess: (v - pad) / scale clamped to [1, org - 1]; gt_bbox_postprocess: no clamp; true fp32 divisions)
+ * and compute_tp (IoU as iou_np, same class, the 10 COCO thresholds) per image.
+ *  det [B][max_keep][6], nkeep [B]: what yh_nms_batched writes.  gt [B][maxbox][gt_ld], gt_ld >= 5: xmin, ymin, xmax, ymax, cls —
+ *  the collate format; a row with cls < 0 is padding, anywhere in the list.  info [B][5]: scale, pad_top, pad_left, org_h, org_w.
+ *  thr: n_thr <= 16 doubles in HOST memory, ascending (read during the call; thr[0] is the matching threshold).
+ * An image counts iff nkeep[b] > 0 and it has a valid ground-truth row (the rule of mAP_v2.__init__).  Per image and row
+ * p < nkeep[b] (rows at or past nkeep[b], and every row of an image that does not count, are left untouched):
+ *  box [B][max_keep][4] the detection in the original frame; conf; cls (int32); iou: the matched IoU, 0 when unmatched; gt_idx: the
+ *  matched row of gt, -1 when unmatched; tp (uint16): bit k set iff matched and (double)iou >= thr[k].
+ *  nrow [B]: nkeep[b] if the image counts, else 0.  gt_hist [num_class] int32 is ACCUMULATED (integer atomics; zero it before the
+ *  first batch): the classes of the valid ground truth of the images that count.
+ * Detection p is matched to the valid ground truth of its class with the largest IoU >= thr[0]; a ground truth claimed by several
+ * detections keeps the LOWEST p (compute_tp's second np.unique), the others are unmatched.  Exact IoU ties between two ground
+ * truths of one detection are outside the host code's contract (unstable sort); here the lowest ground-truth row wins.
+ * YH_EINVAL: a NULL pointer, gt_ld < 5, n_thr outside 1..16, a non-positive size.  Enqueues only: no allocation, no sync. */
+int yh_val_match(const float* det, const int32_t* nkeep, const float* gt, const float* info, int B, int max_keep, int maxbox,
+                 int gt_ld, int num_class, const double* thr, int n_thr, float* box, float* conf, int32_t* cls, float* iou,
+                 int32_t* gt_idx, uint16_t* tp, int32_t* nrow, int32_t* gt_hist, yh_stream stream);
 
 /* ------------------------------------------------------------------------
  * Program executor: replay a pre-built list of launches with one call (the engine's forward / backward programs; replaces the

@@ -26,7 +26,7 @@ sys.path.insert(0, ROOT)
 from config.config import Config                                                    # noqa: E402
 from yoloseries_amd import models                                                   # noqa: E402
 from yoloseries_amd.loss import YOLOV5Loss                                          # noqa: E402
-from yoloseries_amd.trainer import ExponentialMovingAverageModel, YOLOV5Evaluator   # noqa: E402
+from yoloseries_amd.trainer import ExponentialMovingAverageModel, MatchAccumulator, YOLOV5Evaluator   # noqa: E402
 from yoloseries_amd.utils import FlatSGD, mAP_v2                                    # noqa: E402
 from yoloseries_amd.utils.dist import (DataParallelGrads, all_reduce_norm, get_local_rank, get_rank, get_world_size,
                                        synchronize)                                # noqa: E402
@@ -263,15 +263,31 @@ class Training:
         model.eval()
         self.validate.yolo = model
         all_gts, all_preds = [], []
+        acc = MatchAccumulator(self.hyp['num_class'], self.device) if self.hyp.get('device_metric', False) else None
         for x in self.val_dataloader:
+            if acc is not None:
+                # the match table stays on the device.  The boxes go through the validation driver's frame change: the batch's
+                # resize_info where the loader has one, else the network input's own frame (scale 1, no pads; the clamp to
+                # [1, size - 1] is all that is left of it) — the host loop below compares in the letterboxed frame, unclamped
+                info = x.get('resize_info')
+                if info is None:
+                    info = torch.tensor([[1., 0., 0., x['img'].shape[2], x['img'].shape[3]]]).repeat(x['img'].shape[0], 1)
+                acc.append(self.validate.evaluate_matches(x['img'], x['ann'], info, gt_hist=acc.gt_hist))
+                continue
             outs = self.validate(x['img'])
             ann = x['ann'].cpu().numpy()
             for b, o in enumerate(outs):
                 gt = ann[b][ann[b][:, 4] >= 0][:, :5]
                 all_gts.append(gt)
                 all_preds.append(o.numpy() if o is not None else np.zeros((0, 6), np.float32))
-        m, m50, mp, mr = mAP_v2(all_gts, all_preds).get_mean_metrics() if any(len(p) for p in all_preds) else (0., 0., 0., 0.)
-        self.last_metrics = dict(map=m, map50=m50, precision=mp, recall=mr, n_pred=int(sum(len(p) for p in all_preds)))
+        if acc is not None:
+            conf, cls, tp, gt_hist = acc.finish()        # the one device-to-host copy of the pass
+            n_pred = len(conf)
+            m, m50, mp, mr = mAP_v2.from_matches(conf, cls, tp, gt_hist).get_mean_metrics() if n_pred else (0., 0., 0., 0.)
+        else:
+            n_pred = int(sum(len(p) for p in all_preds))
+            m, m50, mp, mr = mAP_v2(all_gts, all_preds).get_mean_metrics() if n_pred else (0., 0., 0., 0.)
+        self.last_metrics = dict(map=m, map50=m50, precision=mp, recall=mr, n_pred=n_pred)
         if self.rank == 0:
             print(f"[eval] epoch {epoch}: mAP {m:.4f} mAP50 {m50:.4f} P {mp:.4f} R {mr:.4f} ({self.last_metrics['n_pred']} boxes)", flush=True)
         model.train(was_training)
@@ -342,6 +358,8 @@ def main(argv=None, training_cls=None, default_cfg=None):
     ap.add_argument("--multi-scale-budget-gb", type=float, help="with --multi-scale: GiB of device memory that the cached per-shape "
                     f"programs (activation and gradient buffers) may hold; least-recently-used shapes are rebuilt when they return. "
                     f"Default: {MULTI_SCALE_FREE_FRACTION:.0%} of the device memory free when training starts")
+    ap.add_argument("--device-metric", action="store_true", help="the evaluation after an epoch matches its detections against the "
+                    "ground truth on the GPU (yh_val_match) and copies one match table to the host at its end")
     args = ap.parse_args(argv)
     if args.deterministic:                                               # before any model / program is built
         import yoloseries_amd
@@ -370,6 +388,7 @@ def main(argv=None, training_cls=None, default_cfg=None):
         if hyp.get('device_letterbox', False):
             ap.error("--augment and --device-letterbox are two ingest paths: the augmentation already runs on the device")
     if args.multi_scale: hyp['mutil_scale_training'] = True              # noqa: E701
+    if args.device_metric: hyp['device_metric'] = True                   # noqa: E701
     if args.multi_scale_budget_gb is not None: hyp['multi_scale_budget_gb'] = args.multi_scale_budget_gb   # noqa: E701
     if training_cls is not None:                                         # train_yolox.py:808: Training(hyp)
         t = training_cls(hyp)

@@ -233,6 +233,8 @@ _SIGS = {
     "yh_exec": (_i32, [C.POINTER(Cmd), _i32, C.POINTER(_vp), _i32, C.POINTER(_i32)]),
     "yh_nms_ws_bytes": (_sz, [_i32, _i32]),
     "yh_nms_batched": (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "yh_val_match": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _i32,
+                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 

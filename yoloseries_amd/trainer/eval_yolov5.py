@@ -16,7 +16,7 @@ from .. import _lib
 from .._lib import DecodeDesc, ViewXform, check, lib
 from ..layout import to_cell_major
 
-__all__ = ['YOLOV5Evaluator']
+__all__ = ['YOLOV5Evaluator', 'MatchAccumulator', 'info_tensor']
 
 
 
@@ -28,6 +28,52 @@ def _decode_ws(owner, d, dev):
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
         owner._decode_ws_buf = ws
     return ws.data_ptr()
+
+IOU_THRESHOLDS = tuple(np.linspace(0.5, 0.95, 10).tolist())        # mAP_v2.iou_thr
+
+
+def info_tensor(info):
+    """the batch's resize_info dicts (dataset/data_collater.py) -> (B, 5) float32 [scale, pad_top, pad_left, org_h, org_w], built
+    once per batch on the host; a tensor passes through"""
+    if torch.is_tensor(info):
+        return info.to(torch.float32).contiguous()
+    rows = [[r['scale'], r['pad_top'], r['pad_left'], r['org_shape'][0], r['org_shape'][1]] for r in info]
+    return torch.from_numpy(np.asarray(rows, dtype=np.float32).reshape(len(rows), 5))
+
+
+class MatchAccumulator:
+    """The match tables of a validation pass, kept on the device: append(evaluate_matches(...)) per batch, finish() once.  Owns the
+    gt_hist buffer that yh_val_match accumulates into (pass acc.gt_hist to evaluate_matches)."""
+
+    def __init__(self, num_class, device):
+        self.num_class = int(num_class)
+        self.gt_hist = torch.zeros(self.num_class, dtype=torch.int32, device=device)
+        self._parts = []
+        self.images = 0
+
+    def append(self, m):
+        if m['gt_hist'] is not self.gt_hist:
+            raise ValueError("MatchAccumulator.append: evaluate_matches was not given this accumulator's gt_hist")
+        self._parts.append((m['conf'], m['cls'], m['tp'], m['nrow']))
+        self.images += m['nrow'].numel()
+
+    def finish(self):
+        """-> (conf (N,) float32, cls (N,) int32, tp (N, 10) bool, gt_hist (num_class,) int64) as NumPy, the padded rows compacted
+        away on the device and everything brought over in ONE device-to-host copy (the only point the host waits)"""
+        if self._parts:
+            keep = torch.cat([(torch.arange(c.shape[1], device=c.device)[None, :] < n[:, None]).reshape(-1) for c, _, _, n in self._parts])
+            conf = torch.cat([c.reshape(-1) for c, _, _, _ in self._parts])[keep]
+            cls = torch.cat([c.reshape(-1) for _, c, _, _ in self._parts])[keep]
+            tp = torch.cat([t.reshape(-1) for _, _, t, _ in self._parts])[keep]
+            flat = torch.cat([conf.view(torch.int32), cls, tp.to(torch.int32) & 0xffff, self.gt_hist])
+        else:
+            flat = self.gt_hist
+        h = flat.cpu().numpy()
+        n = (h.size - self.num_class) // 3
+        conf, cls, bits, hist = h[:n].view(np.float32), h[n:2 * n], h[2 * n:3 * n], h[3 * n:]
+        tp = ((bits[:, None] >> np.arange(len(IOU_THRESHOLDS))[None, :]) & 1).astype(bool)
+        return conf.copy(), cls.copy(), tp, hist.astype(np.int64)
+
 
 class YOLOV5Evaluator:
 
@@ -51,19 +97,21 @@ class YOLOV5Evaluator:
     @torch.no_grad()
     def __call__(self, inputs):
         """:param inputs: (b, 3, h, w) -> list (len b) of FloatTensor (n, 6) [xmin, ymin, xmax, ymax, conf, cls] on CPU, or None"""
-        if self.use_tta and self.hyp.get('mutil_label', False):       # through the decoded tensor, like _nms_from_heads
+        outs = self._run_nms(*self._candidates(inputs))
+        return [torch.from_numpy(x) if x is not None else None for x in outs]
+
+    def _candidates(self, inputs):
+        """forward + decode + filter of a batch by the configured path -> candidate table (cand, ncand, B, cap) on the device"""
+        if self.use_tta and self.hyp.get('mutil_label', False):       # through the decoded tensor, like _cand_from_heads
             merge_preds_out, _ = self.test_time_augmentation(inputs)
             if self.hyp.get("wfb", False):
                 raise NotImplementedError("weighted box fusion is outside the HIP hot path (wfb: false in every shipped config)")
-            outs = self.numba_nms(merge_preds_out)
-        elif self.use_tta:
+            return self._filter_decoded(merge_preds_out)
+        if self.use_tta:
             if self.hyp.get("wfb", False):
                 raise NotImplementedError("weighted box fusion is outside the HIP hot path (wfb: false in every shipped config)")
-            outs = self._tta_from_heads(inputs)
-        else:
-            stage_preds = self.yolo(inputs)
-            outs = self._nms_from_heads(stage_preds)
-        return [torch.from_numpy(x) if x is not None else None for x in outs]
+            return self._tta_cand(inputs)
+        return self._cand_from_heads(self.yolo(inputs))
 
     def _desc(self, stage_preds):
         d = DecodeDesc()
@@ -100,7 +148,8 @@ class YOLOV5Evaluator:
         check(lib().yh_decode_full(C.byref(d), ptrs, out.data_ptr(), _lib.stream_ptr()), "yh_decode_full")
         return out
 
-    def _run_nms(self, cand, ncand, B, cap):
+    def _nms_device(self, cand, ncand, B, cap):
+        """yh_nms_batched on a candidate table -> (out (B, max_keep, 6), nkeep (B,)) on the device; nothing is copied or awaited"""
         dev = cand.device
         L = lib()
         max_keep = int(self.hyp['max_predictions_per_img'])
@@ -111,16 +160,58 @@ class YOLOV5Evaluator:
         check(L.yh_nms_batched(cand.data_ptr(), ncand.data_ptr(), B, cap, float(self.iou_threshold),
                                int(bool(self.hyp['agnostic'])), 1, max_keep, int(bool(self.hyp['postprocess_bbox'])),
                                out.data_ptr(), nkeep.data_ptr(), keep.data_ptr(), ws.data_ptr(), _lib.stream_ptr()), "yh_nms_batched")
+        return out, nkeep
+
+    def _run_nms(self, cand, ncand, B, cap):
+        """_nms_device + the copy of its table to the host -> list (len B) of np.ndarray (n, 6) or None"""
+        out, nkeep = self._nms_device(cand, ncand, B, cap)
         nc_h = ncand.cpu().tolist()
         nk_h = nkeep.cpu().tolist()
         self.last_ncand = nc_h                 # candidates that entered NMS per image (bench.py reports boxes/s from it)
         out_h = out.cpu().numpy()
         return [None if nc_h[b] == 0 else out_h[b, :nk_h[b]].copy() for b in range(B)]
 
+    # ------------------------------------------------------------------ metric on the device
+    @torch.no_grad()
+    def evaluate_matches(self, inputs, ann, info, gt_hist=None):
+        """The forward, filter and NMS of __call__, then yh_val_match on the NMS table where it lies: the detections in the ORIGINAL
+        frame and their true-positive matches against `ann`, as device tensors — nothing is copied to the host or awaited.
+        :param ann: (B, maxbox, >= 5) [xmin, ymin, xmax, ymax, cls, ...] in the letterboxed frame, cls < 0 = padding (the collate format)
+        :param info: (B, 5) float32 [scale, pad_top, pad_left, org_h, org_w], or the batch's list of resize_info dicts
+        :param gt_hist: (num_class,) int32 device tensor to accumulate the ground-truth classes into (MatchAccumulator.gt_hist)
+        :return: dict of box (B, K, 4), conf (B, K), cls (B, K) int32, iou (B, K), gt_idx (B, K) int32, tp (B, K) int16 (bit k: IoU
+                 threshold k of mAP_v2, read it as uint16), nrow (B,) int32, gt_hist; rows at or past nrow[b] are undefined"""
+        cand, ncand, B, cap = self._candidates(inputs)
+        det, nkeep = self._nms_device(cand, ncand, B, cap)
+        dev = det.device
+        K = det.shape[1]
+        info = info_tensor(info).to(dev, non_blocking=True)
+        ann = ann.to(device=dev, dtype=torch.float32)
+        if ann.dim() != 3 or ann.shape[0] != B or ann.shape[2] < 5 or tuple(info.shape) != (B, 5):
+            raise ValueError(f"evaluate_matches: ann {tuple(ann.shape)} / info {tuple(info.shape)} do not describe a batch of {B} images")
+        if ann.shape[1] == 0:                                          # no ground truth at all: one padding row per image
+            ann = torch.full((B, 1, 5), -1.0, dtype=torch.float32, device=dev)
+        ann = ann.contiguous()
+        if gt_hist is None:
+            gt_hist = torch.zeros(self.num_class, dtype=torch.int32, device=dev)
+        o = dict(box=torch.empty(B, K, 4, dtype=torch.float32, device=dev), conf=torch.empty(B, K, dtype=torch.float32, device=dev),
+                 cls=torch.empty(B, K, dtype=torch.int32, device=dev), iou=torch.empty(B, K, dtype=torch.float32, device=dev),
+                 gt_idx=torch.empty(B, K, dtype=torch.int32, device=dev), tp=torch.empty(B, K, dtype=torch.int16, device=dev),
+                 nrow=torch.empty(B, dtype=torch.int32, device=dev), gt_hist=gt_hist)
+        thr = (C.c_double * len(IOU_THRESHOLDS))(*IOU_THRESHOLDS)
+        check(lib().yh_val_match(det.data_ptr(), nkeep.data_ptr(), ann.data_ptr(), info.data_ptr(), B, K, ann.shape[1], ann.shape[2],
+                                 self.num_class, thr, len(IOU_THRESHOLDS), o['box'].data_ptr(), o['conf'].data_ptr(), o['cls'].data_ptr(),
+                                 o['iou'].data_ptr(), o['gt_idx'].data_ptr(), o['tp'].data_ptr(), o['nrow'].data_ptr(),
+                                 gt_hist.data_ptr(), _lib.stream_ptr()), "yh_val_match")
+        return o
+
     def _nms_from_heads(self, stage_preds):
         """fused decode + filter + NMS straight from the head tensors (no decoded tensor is materialised)"""
+        return self._run_nms(*self._cand_from_heads(stage_preds))
+
+    def _cand_from_heads(self, stage_preds):
         if self.hyp.get('mutil_label', False):          # one candidate per (prediction, class): through the decoded tensor (:276-279)
-            return self.numba_nms(self.decode(stage_preds))
+            return self._filter_decoded(self.decode(stage_preds))
         d, canon, ptrs = self._desc(stage_preds)
         dev = stage_preds[0].device
         B = d.B
@@ -134,7 +225,7 @@ class YOLOV5Evaluator:
             if cap >= n or int(ncand.max().item()) <= cap:
                 break
             cap = ((n + 3) // 4) * 4
-        return self._run_nms(cand, ncand, B, cap)
+        return cand, ncand, B, cap
 
     _TTA_PASSES = ((1, None), (0.83, 2), (0.67, 3))       # (scale, flipped axis) of test_time_augmentation (:159-160)
     _TTA_FIRST_CAP = 3 * 16384                            # rows per image of the first try: _nms_from_heads' figure per pass
@@ -146,6 +237,10 @@ class YOLOV5Evaluator:
 
     @torch.no_grad()
     def _tta_from_heads(self, inputs):
+        return self._run_nms(*self._tta_cand(inputs))
+
+    @torch.no_grad()
+    def _tta_cand(self, inputs):
         """test_time_augmentation + numba_nms without the decoded tensors: each pass is decoded, filtered, un-scaled and
         un-flipped straight from its heads (yh_decode_filter_view) and appended to one candidate table, in the order of the
         concatenation, before the next forward overwrites the engine's head buffers; one NMS over the table.  Same rows as
@@ -173,7 +268,7 @@ class YOLOV5Evaluator:
             if cap >= n_all or int(ncand.max().item()) <= cap:
                 break
             cap = ((n_all + 3) // 4) * 4                  # one row per prediction of the three passes: cannot overflow
-        return self._run_nms(cand, ncand, B, cap)
+        return cand, ncand, B, cap
 
     _FILTER_MODES = (0, 2)        # yh_filter_decoded mode of the single-label / hyp['mutil_label'] candidate rule (:266-286)
 

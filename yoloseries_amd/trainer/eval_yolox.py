@@ -83,20 +83,20 @@ class YOLOXEvaluator(YOLOV5Evaluator):
         check(lib().yh_decode_full(C.byref(d), ptrs, out.data_ptr(), _lib.stream_ptr()), "yh_decode_full")
         return out
 
-    @torch.no_grad()
-    def __call__(self, inputs):
-        if self.use_tta and self.hyp.get('mutil_label', False):       # through the decoded tensor, like _nms_from_heads
+    def _candidates(self, inputs):
+        if self.use_tta and self.hyp.get('mutil_label', False):       # through the decoded tensor, like _cand_from_heads
             merge_preds_out, _ = self.test_time_augmentation(inputs)
-            outs = self.numba_nms(merge_preds_out)
-        elif self.use_tta:
-            outs = self._tta_from_heads(inputs)                       # inherited; strides per pass from _view_desc
-        else:
-            outs = self._nms_from_heads(self.yolo(inputs), inputs.size(2))
-        return [torch.from_numpy(x) if x is not None else None for x in outs]
+            return self._filter_decoded(merge_preds_out)
+        if self.use_tta:
+            return self._tta_cand(inputs)                             # inherited; strides per pass from _view_desc
+        return self._cand_from_heads(self.yolo(inputs), inputs.size(2))
 
     def _nms_from_heads(self, stage_preds, img_h=None):
+        return self._run_nms(*self._cand_from_heads(stage_preds, img_h))
+
+    def _cand_from_heads(self, stage_preds, img_h=None):
         if self.hyp.get('mutil_label', False):          # one candidate per (prediction, class): through the decoded tensor (eval_yolox.py:218-221)
-            return self.numba_nms(self.decode(stage_preds, img_h))
+            return self._filter_decoded(self.decode(stage_preds, img_h))
         sp = self._stage_list(stage_preds)
         d, canon, ptrs = self._desc(sp)
         self._set_strides(d, img_h if img_h is not None else self.inp_h)
@@ -108,7 +108,7 @@ class YOLOXEvaluator(YOLOV5Evaluator):
         ncand = torch.zeros(B, dtype=torch.int32, device=dev)
         check(lib().yh_decode_filter(C.byref(d), ptrs, float(self.conf_threshold), float(self.cls_threshold),
                                      cand.data_ptr(), ncand.data_ptr(), cap, _decode_ws(self, d, dev), _lib.stream_ptr()), "yh_decode_filter")
-        return self._run_nms(cand, ncand, B, cap)
+        return cand, ncand, B, cap
 
     # candidate rule of this evaluator (eval_yolox.py:206-231): pre-filter on obj * max(cls) >= conf, class confidence >= cls
     # threshold (inclusive, unlike the v5 evaluator); hyp['mutil_label']: one candidate per (prediction, class) (:218-221).

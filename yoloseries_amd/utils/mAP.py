@@ -39,6 +39,20 @@ class mAP_v2:
         self.iou_thr = np.linspace(0.5, 0.95, 10)
         self.save_dir = plot_save_dir
         self.type = type
+        self._tables = None
+
+    @classmethod
+    def from_matches(cls, conf, pcls, tp, gt_hist, plot_save_dir=None, type='coco'):
+        """The metric from a match table instead of box lists (yh_val_match through MatchAccumulator.finish()): conf (N,) and
+        pcls (N,) of every detection of the images that count, tp (N, 10) bool — compute_tp's rows — and gt_hist, the number of
+        ground-truth boxes per class of those images.  Same results as the list constructor on the same detections."""
+        self = cls([], [], plot_save_dir, type)
+        tp = np.asarray(tp, dtype=bool).reshape(-1, len(self.iou_thr))
+        conf, pcls, gt_hist = np.asarray(conf), np.asarray(pcls), np.asarray(gt_hist)
+        assert len(conf) == len(pcls) == len(tp) and gt_hist.ndim == 1
+        tot_cls = np.nonzero(gt_hist)[0]
+        self._tables = (tp, conf, pcls, tot_cls, gt_hist[tot_cls])
+        return self
 
     def compute_tp(self, gt, pred):
         tp = np.zeros(shape=(pred.shape[0], len(self.iou_thr)), dtype=bool)
@@ -67,21 +81,28 @@ class mAP_v2:
             ap = np.sum((rec[i + 1] - rec[i]) * pre[i + 1])
         return ap, rec, pre
 
-    def compute_ap_per_class(self):
+    def match_tables(self):
+        """-> (tp (N, 10) bool, conf (N,), pcls (N,), unique ground-truth classes, ground-truth boxes of each of them)"""
+        if self._tables is not None:
+            return self._tables
         tps = np.concatenate([self.compute_tp(g, p) for g, p in zip(self.gt, self.pred)], axis=0)
         pred_all = np.concatenate(self.pred, axis=0)
         gt_all = np.concatenate(self.gt, axis=0)
-        conf, pcls, tcls = pred_all[:, 4], pred_all[:, 5], gt_all[:, 4]
+        tcls = gt_all[:, 4]
+        tot_cls = np.unique(tcls)
+        return tps, pred_all[:, 4], pred_all[:, 5], tot_cls, np.array([(tcls == c).sum() for c in tot_cls], dtype=np.int64)
+
+    def compute_ap_per_class(self):
+        tps, conf, pcls, tot_cls, num_tars = self.match_tables()
         sort_i = np.argsort(conf)[::-1]
         stp, scof, scls = tps[sort_i], conf[sort_i], pcls[sort_i]
-        tot_cls = np.unique(tcls)
         ap = np.zeros((len(tot_cls), stp.shape[1]))
         precision = np.zeros(shape=[len(tot_cls), 1000])
         recall = np.zeros(shape=[len(tot_cls), 1000])
         xs = np.linspace(0, 1, 1000)
         for i, c in enumerate(tot_cls):
             mi = scls == c
-            num_tar = (tcls == c).sum()
+            num_tar = num_tars[i]
             if mi.sum() > 0 and num_tar > 0:
                 cfp = (~stp[mi]).cumsum(0)
                 ctp = stp[mi].cumsum(0)
