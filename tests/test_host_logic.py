@@ -774,13 +774,16 @@ def test_inline_asm_loads_are_not_read_before_their_wait(tmp_path):
     """conv_halo160_kernel requests its fragments by inline-asm ds_read and waits for them by an inline-asm s_waitcnt tied to the
     destination registers.  The compiler believes those registers defined at the ds_read: should it ever copy or use one in front
     of the wait (it did exactly that to conv_pt_kernel's operand loads in round 5), the copy holds stale bytes.  The generated
-    code of every kernel of conv_igemm.hip is scanned: no compiler-generated instruction reads such a register before the wait."""
+    code of every kernel of the generic conv (one file per kernel family beside the planner, conv_igemm.hip) is scanned: no
+    compiler-generated instruction reads such a register before the wait."""
     import subprocess
-    src = os.path.join(ROOT, "yoloseries_amd", "csrc", "conv_igemm.hip")
-    out = tmp_path / "igemm.s"
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast", "--cuda-device-only", "-S",
-                    "-o", str(out), src], check=True, capture_output=True)
-    text = out.read_text()
+    text = ""
+    for family in ("conv_generic", "conv_v2", "conv_v3", "conv_halo", "conv_halo160", "conv_stem"):
+        src = os.path.join(ROOT, "yoloseries_amd", "csrc", family + ".hip")
+        out = tmp_path / (family + ".s")
+        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast", "--cuda-device-only", "-S",
+                        "-o", str(out), src], check=True, capture_output=True)
+        text += out.read_text()
     assert "conv_halo160_kernel" in text and len(re.findall(r";;#ASMSTART\n\s*ds_read_b128", text)) >= 10
     hits = _asm_pending_reads(text)
     assert not hits, hits[:5]

@@ -1,6 +1,6 @@
 // Flat parameter-arena kernels: index-map gather between the fp32 master parameters
 // (PyTorch OIHW layout, state_dict compatible) and the packed bf16 weight images read
-// by conv_igemm.hip, plus the optimizer-side streaming kernels (SGD-nesterov with
+// by the convolution kernels (conv_igemm.hip plans them), plus the optimizer-side streaming kernels (SGD-nesterov with
 // per-element parameter groups, grad-norm, EMA) of train_yolov5.py:258-280,342-350 and
 // trainer/ema_model.py:20-28.  All HBM-bound, one launch per step each.
 #include "common.h"

@@ -86,18 +86,24 @@ void yh_set_error(const char* fmt, ...);
 // it there too.  One flag per device (bit mask over the first 64 devices, others set the attribute at every launch), written only
 // after every hipFuncSetAttribute of the block has succeeded; two threads may both set the attributes (idempotent), none launches
 // before they are set.  A failed set leaves the flag clear and the launch behind it reports hipErrorInvalidValue (YH_CHECK_LAUNCH).
+// The flags are all the threads share: whether a block succeeded is judged from a local of the thread that ran it.
 #include <atomic>
-struct YhDevOnce {
-    std::atomic<uint64_t> mask{0};
-    bool failed = false;
-    static int dev_() { int d = -1; return hipGetDevice(&d) == hipSuccess ? d : -1; }
-    bool need() { const int d = dev_(); failed = false; return d < 0 || d >= 64 || !((mask.load(std::memory_order_acquire) >> d) & 1ull); }
-    void set(const void* fn, hipFuncAttribute attr, int value) {
-        const hipError_t e = hipFuncSetAttribute(fn, attr, value);
-        if (e != hipSuccess) { failed = true; yh_set_error("hipFuncSetAttribute(%d bytes of LDS): %s", value, hipGetErrorString(e)); }
+#include <initializer_list>
+struct YhDevOnce { std::atomic<uint64_t> mask{0}; };
+struct YhLdsLimit { const void* kernel; int bytes; };
+// raises the dynamic-LDS limit of every listed kernel on the current device, unless `once` says it has been done there
+inline void yh_lds_limit(YhDevOnce& once, std::initializer_list<YhLdsLimit> limits)
+{
+    int dev = -1;
+    const bool flagged = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
+    if (flagged && ((once.mask.load(std::memory_order_acquire) >> dev) & 1ull)) return;
+    bool ok = true;
+    for (const YhLdsLimit& l : limits) {
+        const hipError_t e = hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l.bytes);
+        if (e != hipSuccess) { ok = false; yh_set_error("hipFuncSetAttribute(%d bytes of LDS): %s", l.bytes, hipGetErrorString(e)); }
     }
-    void done() { const int d = dev_(); if (!failed && d >= 0 && d < 64) mask.fetch_or(1ull << d, std::memory_order_release); }
-};
+    if (ok && flagged) once.mask.fetch_or(1ull << dev, std::memory_order_release);
+}
 #define YH_CHECK_ARG(cond, ...) do { if (!(cond)) { yh_set_error(__VA_ARGS__); return YH_EINVAL; } } while (0)
 #define YH_CHECK_LAUNCH(name) do { hipError_t e_ = hipGetLastError(); \
     if (e_ != hipSuccess) { yh_set_error("%s: launch failed: %s", name, hipGetErrorString(e_)); return YH_ELAUNCH; } } while (0)

@@ -401,11 +401,7 @@ int yh_dg2_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name
     do {                                                                                                               \
         const int sm = dg_smem_bytes<CT_, KC_, PT_>();                                                                 \
         static YhDevOnce attr_set;                                                                                        \
-        if (attr_set.need()) {                                                                                               \
-            attr_set.set((const void*)conv_dg2_kernel<CT_, KC_, 0, PT_>, hipFuncAttributeMaxDynamicSharedMemorySize, sm); \
-            attr_set.set((const void*)conv_dg2_kernel<CT_, KC_, 3, PT_>, hipFuncAttributeMaxDynamicSharedMemorySize, sm); \
-            attr_set.done();                                                                                            \
-        }                                                                                                              \
+        yh_lds_limit(attr_set, {{(const void*)conv_dg2_kernel<CT_, KC_, 0, PT_>, sm}, {(const void*)conv_dg2_kernel<CT_, KC_, 3, PT_>, sm}}); \
         if (epi == 3) conv_dg2_kernel<CT_, KC_, 3, PT_><<<grid, blk, sm, st>>>(pl.k);                                  \
         else          conv_dg2_kernel<CT_, KC_, 0, PT_><<<grid, blk, sm, st>>>(pl.k);                                  \
     } while (0)

@@ -408,12 +408,8 @@ int yh_p3_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_
     do {                                                                                                               \
         const int sm = p3_smem_bytes<CT_, KC_, PT_>();                                                                 \
         static YhDevOnce attr_set;                                                                                        \
-        if (attr_set.need()) {                                                                                               \
-            attr_set.set((const void*)conv_p3_kernel<CT_, KC_, 0, PT_>, hipFuncAttributeMaxDynamicSharedMemorySize, sm); \
-            attr_set.set((const void*)conv_p3_kernel<CT_, KC_, 1, PT_>, hipFuncAttributeMaxDynamicSharedMemorySize, sm); \
-            attr_set.set((const void*)conv_p3_kernel<CT_, KC_, 3, PT_>, hipFuncAttributeMaxDynamicSharedMemorySize, sm); \
-            attr_set.done();                                                                                            \
-        }                                                                                                              \
+        yh_lds_limit(attr_set, {{(const void*)conv_p3_kernel<CT_, KC_, 0, PT_>, sm}, {(const void*)conv_p3_kernel<CT_, KC_, 1, PT_>, sm}, \
+                                {(const void*)conv_p3_kernel<CT_, KC_, 3, PT_>, sm}});                                    \
         if (epi == 3)      conv_p3_kernel<CT_, KC_, 3, PT_><<<grid, blk, sm, st>>>(pl.k);                              \
         else if (epi == 1) conv_p3_kernel<CT_, KC_, 1, PT_><<<grid, blk, sm, st>>>(pl.k);                              \
         else               conv_p3_kernel<CT_, KC_, 0, PT_><<<grid, blk, sm, st>>>(pl.k);                              \
@@ -422,11 +418,7 @@ int yh_p3_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_
     do {                                                                                                               \
         const int sm = p3_smem_bytes<CT_, 32, PT_, 2>();                                                               \
         static YhDevOnce attr_set;                                                                                     \
-        if (attr_set.need()) {                                                                                         \
-            attr_set.set((const void*)conv_p3_kernel<CT_, 32, 0, PT_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, sm); \
-            attr_set.set((const void*)conv_p3_kernel<CT_, 32, 1, PT_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, sm); \
-            attr_set.done();                                                                                           \
-        }                                                                                                              \
+        yh_lds_limit(attr_set, {{(const void*)conv_p3_kernel<CT_, 32, 0, PT_, 2>, sm}, {(const void*)conv_p3_kernel<CT_, 32, 1, PT_, 2>, sm}}); \
         if (epi == 1) conv_p3_kernel<CT_, 32, 1, PT_, 2><<<grid, blk, sm, st>>>(pl.k);                                 \
         else          conv_p3_kernel<CT_, 32, 0, PT_, 2><<<grid, blk, sm, st>>>(pl.k);                                 \
     } while (0)

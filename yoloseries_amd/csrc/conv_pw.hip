@@ -285,11 +285,7 @@ int yh_pw_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_
     do {                                                                                                               \
         constexpr int sm = PwCfg<CIN_, 5, TMW_>::SMEM;                                                                    \
         static YhDevOnce attr_set;                                                                                        \
-        if (attr_set.need()) {                                                                                               \
-            attr_set.set((const void*)conv_pw_kernel<CIN_, 5, TMW_, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, sm); \
-            attr_set.set((const void*)conv_pw_kernel<CIN_, 5, TMW_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, sm); \
-            attr_set.done();                                                                                            \
-        }                                                                                                              \
+        yh_lds_limit(attr_set, {{(const void*)conv_pw_kernel<CIN_, 5, TMW_, 0>, sm}, {(const void*)conv_pw_kernel<CIN_, 5, TMW_, 2>, sm}}); \
         if (pl.epi == 2) conv_pw_kernel<CIN_, 5, TMW_, 2><<<grid, blk, sm, st>>>(pl.k);                                      \
         else             conv_pw_kernel<CIN_, 5, TMW_, 0><<<grid, blk, sm, st>>>(pl.k);                                      \
     } while (0)

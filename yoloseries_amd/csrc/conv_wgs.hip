@@ -538,14 +538,9 @@ static void wgs_fill(const yh_wgrad_desc* d, const WgsPlan& pl, int G, WgsK* kp)
 
 static void wgs_attrs()
 {
-    static YhDevOnce attr_set;      
-    if (attr_set.need()) {
-        attr_set.set((const void*)conv_wgs_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, WGS_LDS);
-        attr_set.set((const void*)conv_wgs_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, WGS_LDS);
-        attr_set.set((const void*)conv_wgs_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, WGS_LDS);
-        attr_set.set((const void*)conv_wgs_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, WGS_LDS);
-        attr_set.done(); 
-    }
+    static YhDevOnce attr_set;
+    yh_lds_limit(attr_set, {{(const void*)conv_wgs_kernel<true>, WGS_LDS}, {(const void*)conv_wgs_kernel<false>, WGS_LDS},
+                            {(const void*)conv_wgs_kernel<true, true>, WGS_LDS}, {(const void*)conv_wgs_kernel<false, true>, WGS_LDS}});
 }
 
 int yh_wgs_run(const yh_wgrad_desc* d, yh_stream stream)

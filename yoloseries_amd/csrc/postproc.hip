@@ -671,11 +671,11 @@ int decode_filter_launch(const yh_decode_desc* d, const void* const* preds, cons
         char label[64];
         if (d->pred_is_f32) {
             static YhDevOnce attr;
-            if (attr.need()) { attr.set((const void*)decode_scan_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr.done(); }
+            yh_lds_limit(attr, {{(const void*)decode_scan_kernel<float>, 160 * 1024}});
             hipLaunchKernelGGL((decode_scan_kernel<float>), grid, dim3(256), sm, (hipStream_t)stream, k, v, conf_thr, cls_thr, stage, counts, nkeys);
         } else {
             static YhDevOnce attr;
-            if (attr.need()) { attr.set((const void*)decode_scan_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr.done(); }
+            yh_lds_limit(attr, {{(const void*)decode_scan_kernel<uint16_t>, 160 * 1024}});
             hipLaunchKernelGGL((decode_scan_kernel<uint16_t>), grid, dim3(256), sm, (hipStream_t)stream, k, v, conf_thr, cls_thr, stage, counts, nkeys);
         }
         snprintf(label, sizeof(label), "%s(scan)", who);

@@ -194,13 +194,8 @@ extern "C" int yh_sppf_pool3_fwd(const yh_bf16* x, int ldx, int B, int H, int W,
     const int ch = sppf_ch(H * W);
     const size_t sm = sppf_smem(H * W, ch);
     static YhDevOnce attr;
-    if (attr.need()) {
-        const int mx = (int)sppf_smem(SP_MAXPX, 32);
-        attr.set((const void*)sppf_pool3_fwd_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        attr.set((const void*)sppf_pool3_fwd_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        attr.set((const void*)sppf_pool3_fwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        attr.done();
-    }
+    const int mx = (int)sppf_smem(SP_MAXPX, 32);
+    yh_lds_limit(attr, {{(const void*)sppf_pool3_fwd_kernel<32>, mx}, {(const void*)sppf_pool3_fwd_kernel<16>, mx}, {(const void*)sppf_pool3_fwd_kernel<8>, mx}});
     const dim3 grid(B, (C + ch - 1) / ch), blk(SP_NT);
     if (ch == 32)      sppf_pool3_fwd_kernel<32><<<grid, blk, sm, (hipStream_t)stream>>>(x, ldx, H, W, C, o1, o2, o3, ldo, i1, i2, i3);
     else if (ch == 16) sppf_pool3_fwd_kernel<16><<<grid, blk, sm, (hipStream_t)stream>>>(x, ldx, H, W, C, o1, o2, o3, ldo, i1, i2, i3);
@@ -218,13 +213,8 @@ extern "C" int yh_sppf_pool3_bwd(const yh_bf16* g1, const yh_bf16* g2, const yh_
     const int ch = sppf_ch(H * W);
     const size_t sm = sppf_smem(H * W, ch);
     static YhDevOnce attr;
-    if (attr.need()) {
-        const int mx = (int)sppf_smem(SP_MAXPX, 32);
-        attr.set((const void*)sppf_pool3_bwd_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        attr.set((const void*)sppf_pool3_bwd_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        attr.set((const void*)sppf_pool3_bwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        attr.done();
-    }
+    const int mx = (int)sppf_smem(SP_MAXPX, 32);
+    yh_lds_limit(attr, {{(const void*)sppf_pool3_bwd_kernel<32>, mx}, {(const void*)sppf_pool3_bwd_kernel<16>, mx}, {(const void*)sppf_pool3_bwd_kernel<8>, mx}});
     const dim3 grid(B, (C + ch - 1) / ch), blk(SP_NT);
     if (ch == 32)      sppf_pool3_bwd_kernel<32><<<grid, blk, sm, (hipStream_t)stream>>>(g1, g2, g3, ldg, i1, i2, i3, H, W, C, gx, ldx, accumulate);
     else if (ch == 16) sppf_pool3_bwd_kernel<16><<<grid, blk, sm, (hipStream_t)stream>>>(g1, g2, g3, ldg, i1, i2, i3, H, W, C, gx, ldx, accumulate);
