@@ -571,6 +571,26 @@ int yh_nms_batched(const float* cand, const int32_t* ncand, int B, int cap,
 int yh_val_match(const float* det, const int32_t* nkeep, const float* gt, const float* info, int B, int max_keep, int maxbox,
                  int gt_ld, int num_class, const double* thr, int n_thr, float* box, float* conf, int32_t* cls, float* iou,
                  int32_t* gt_idx, uint16_t* tp, int32_t* nrow, int32_t* gt_hist, yh_stream stream);
+/* The rest of the metric on the device: the match table of a whole pass to the per-class AP and the precision / recall curves of
+ * utils/mAP.py compute_ap_per_class / compute_ap (yoloseries_amd/csrc/metric.hip lists the operation order: fp64, each operation once).
+ *  conf [N] fp32, cls [N] int32, tp [N] uint16 (bit k: IoU threshold k): the compacted rows of the images that count, as yh_val_match
+ *  wrote them.  order [N] int32: a permutation of the rows, class ascending, then conf descending — the library does not sort.
+ *  gt_hist [num_class] int32.  xs_ap [n_ap], xs_pr [n_pr] doubles in DEVICE memory, ascending: np.linspace(0, 1, 101) and
+ *  np.linspace(0, 1, 1000), made by the caller (i * step and i / n differ in the last bit); 2 <= n_ap <= 1024, n_pr >= 1.
+ *  ap [num_class][n_thr], precision [num_class][n_pr], recall [num_class][n_pr] doubles (the curves are threshold 0's);
+ *  npred [num_class] int32: the rows of the class, counted or not.  Every element of the four is written on every call; ap,
+ *  precision and recall of a class with gt_hist[c] <= 0 or without a row are zeros.  ap is the trapezoid sum over xs_ap added left
+ *  to right (np.sum adds pairwise: a few ulp apart).
+ *  ws: yh_val_ap_ws_bytes(N, n_thr) bytes, 4-byte aligned (the cumulative true positives per row and threshold).
+ * Outside the contract: two rows of one class with equal conf and different tp masks (the host's order there comes from an unstable
+ * sort; here `order` decides — with a stable sort the lower original row comes first); NaN or negative conf; a class with more
+ * true positives than ground truth.  An entry of order outside [0, N) is clamped, never followed.
+ * YH_EINVAL: a NULL pointer, non-positive N or num_class, n_thr outside 1..16, n_ap outside 2..1024, n_pr < 1, an unaligned table.
+ * One launch, a workgroup per (class, threshold).  Enqueues only: no allocation, no sync. */
+size_t yh_val_ap_ws_bytes(int N, int n_thr);
+int yh_val_ap(const float* conf, const int32_t* cls, const uint16_t* tp, const int32_t* order, int N, const int32_t* gt_hist,
+              int num_class, int n_thr, const double* xs_ap, int n_ap, const double* xs_pr, int n_pr, double* ap, double* precision,
+              double* recall, int32_t* npred, void* ws, yh_stream stream);
 
 /* ------------------------------------------------------------------------
  * Program executor: replay a pre-built list of launches with one call (the engine's forward / backward programs; replaces the

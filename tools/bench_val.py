@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 """What --device-metric buys a validation pass: the loop of val_yolov5.Training.step over the same batches, host tail
 (evaluator -> rows to the host -> preds_postprocess / gt_bbox_postprocess -> mAP_v2(gts, preds)) against device tail
-(evaluate_matches -> MatchAccumulator -> mAP_v2.from_matches), and the yh_val_match launch alone.
+(evaluate_matches -> MatchAccumulator -> mAP_v2.from_matches), against the device tail with the AP on the device too (--device-ap:
+MatchAccumulator.finish_ap -> mAP_v2.from_curves), and the yh_val_match and yh_val_ap launches alone.
 
 YOLOv5s with random weights, the shipped configuration (test-time augmentation on unless --no-tta), --batches batches of the
 synthetic loader, letterboxed once and kept on the device, so that the loader's host work (the same in both modes) is not in the
 window.  The evaluator's confidence / class threshold is picked from a grid on the first batch so that NMS keeps on the order of
 100 rows per image; where random weights reach that at no threshold, the heads come from synth_nms_heads through a stub that still
-runs the network (its forward stays in the window) — the result says which ("heads").  The two modes alternate; each figure is the
+runs the network (its forward stays in the window) — the result says which ("heads").  The three modes alternate; each figure is the
 median of --reps runs after one warm-up, a run timed from its first batch to the synchronize behind its last, the metric behind it
-timed on its own ("metric_s": compute_tp is in it on the host path and on the device on the other).  The kernel: events around 50
-launches after 10 warm-ups on the first batch's tables.
+timed on its own ("metric_s": compute_tp is in it on the host path and on the device on the others; with device_ap the sort, the
+yh_val_ap launch and the copy of the curves are in "loop_s", like finish(), and "metric_s" is what is left for the host).  The kernels:
+events around 50 launches after 10 warm-ups, yh_val_match on the first batch's tables, yh_val_ap on the whole pass's compacted table
+(its key build + sort timed the same way next to it).
 
     python tools/bench_val.py [--img 640] [--batch 64] [--batches 16] [--reps 5] [--no-tta] [--out profiles/val_metric.json]
 """
@@ -30,7 +33,7 @@ import val_yolov5                                                               
 from config.config import Config                                                    # noqa: E402
 from yoloseries_amd import _lib                                                     # noqa: E402
 from yoloseries_amd.trainer import MatchAccumulator                                 # noqa: E402
-from yoloseries_amd.trainer.eval_yolov5 import IOU_THRESHOLDS, info_tensor          # noqa: E402
+from yoloseries_amd.trainer.eval_yolov5 import AP_GRID, IOU_THRESHOLDS, PR_GRID, info_tensor   # noqa: E402
 from yoloseries_amd.utils import mAP_v2                                             # noqa: E402
 from yoloseries_amd.utils.synth import COCO_ANCHORS, synth_nms_heads                # noqa: E402
 
@@ -100,6 +103,15 @@ def device_pass(ev, batches, num_class, dev):
     return lambda: mAP_v2.from_matches(conf, cls, tp, hist).get_mean_metrics(), len(conf)
 
 
+def device_ap_pass(ev, batches, num_class, dev):
+    acc = MatchAccumulator(num_class, dev)
+    for x in batches:
+        acc.append(ev.evaluate_matches(x['img'], x['ann'], x['resize_info'], gt_hist=acc.gt_hist))
+    ap, precision, recall, npred, hist = acc.finish_ap()
+    torch.cuda.synchronize()
+    return lambda: mAP_v2.from_curves(ap, precision, recall, hist).get_mean_metrics(), int(npred.sum())
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -137,6 +149,76 @@ def kernel_ms(ev, x, num_class, launches=50, warm=10):
                                                 matched=int((o[4][torch.arange(K, device=dev)[None] < o[6][:, None]] >= 0).sum()))
 
 
+def tie_report(conf, cls, tp):
+    """how far the pass's table is from the condition under which the host's unstable argsort and the device's stable order must
+    agree: rows that share (class, confidence) with another row, and those of them whose group holds different TP masks"""
+    bits = (tp.astype(np.int64) << np.arange(tp.shape[1])).sum(1)
+    key = (cls.astype(np.int64) << 32) | conf.view(np.uint32).astype(np.int64)
+    order = np.lexsort((bits, key))
+    k, b = key[order], bits[order]
+    first = np.nonzero(np.r_[True, k[1:] != k[:-1]])[0]
+    size = np.diff(np.r_[first, len(k)])
+    mixed = np.minimum.reduceat(b, first) != np.maximum.reduceat(b, first)
+    return dict(rows=len(k), distinct_class_conf=len(first), rows_in_tied_groups=int(size[size > 1].sum()),
+                rows_in_tied_groups_with_different_masks=int(size[mixed].sum()))
+
+
+def restatement_check(ev, batches, num_class, dev):
+    """the device's curves on the pass's table against the NumPy restatement of the tests (stable order, left-to-right sum): bit for bit"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_val_ap_host import order_ref, val_ap_ref
+    acc = MatchAccumulator(num_class, dev)
+    for x in batches:
+        acc.append(ev.evaluate_matches(x['img'], x['ann'], x['resize_info'], gt_hist=acc.gt_hist))
+    conf, cls, tp, hist = acc.finish()
+    ap, precision, recall, npred, _ = acc.finish_ap()
+    bits = (tp.astype(np.uint16) << np.arange(tp.shape[1], dtype=np.uint16)).sum(1).astype(np.uint16)
+    ref = val_ap_ref(conf, cls, bits, order_ref(conf, cls), hist)
+    same = all(np.array_equal(a.view(np.uint64), ref[k].view(np.uint64)) for a, k in ((ap, "ap"), (precision, "precision"), (recall, "recall")))
+    return dict(tie_report(conf, cls, tp), device_equals_restatement_bit_for_bit=bool(same and np.array_equal(npred, ref["npred"])))
+
+
+def _event_ms(fn, launches, warm):
+    for _ in range(warm):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(launches):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / launches
+
+
+@torch.no_grad()
+def ap_kernel_ms(ev, batches, num_class, dev, launches=50, warm=10):
+    """yh_val_ap alone on the compacted table of the whole pass, and the key build + stable sort in front of it"""
+    acc = MatchAccumulator(num_class, dev)
+    for x in batches:
+        acc.append(ev.evaluate_matches(x['img'], x['ann'], x['resize_info'], gt_hist=acc.gt_hist))
+    conf, cls, tp = (t.contiguous() for t in acc._compact())
+    n, nt = conf.numel(), len(IOU_THRESHOLDS)
+
+    def sort():
+        key = (cls.to(torch.int64) << 32) | (0xFFFFFFFF - (conf.view(torch.int32).to(torch.int64) & 0xFFFFFFFF))
+        return torch.sort(key, stable=True)[1].to(torch.int32)
+    order = sort()
+    xs = torch.from_numpy(np.concatenate((np.linspace(0, 1, AP_GRID), np.linspace(0, 1, PR_GRID)))).to(dev)
+    o = [torch.empty(num_class * nt, dtype=torch.float64, device=dev), torch.empty(num_class * PR_GRID, dtype=torch.float64, device=dev),
+         torch.empty(num_class * PR_GRID, dtype=torch.float64, device=dev), torch.empty(num_class, dtype=torch.int32, device=dev),
+         torch.empty(max(int(_lib.lib().yh_val_ap_ws_bytes(n, nt)), 16), dtype=torch.uint8, device=dev)]
+
+    def launch():
+        _lib.check(_lib.lib().yh_val_ap(conf.data_ptr(), cls.data_ptr(), tp.data_ptr(), order.data_ptr(), n, acc.gt_hist.data_ptr(), num_class,
+                                        nt, xs.data_ptr(), AP_GRID, xs[AP_GRID:].data_ptr(), PR_GRID, *[t.data_ptr() for t in o],
+                                        _lib.stream_ptr()), "yh_val_ap")
+    k_ms = _event_ms(launch, launches, warm)
+    s_ms = _event_ms(sort, launches, warm)
+    seg = torch.bincount(cls.clamp(0, num_class - 1), minlength=num_class)
+    return dict(ms_per_launch=k_ms, key_and_sort_ms=s_ms, rows=n, num_class=num_class, n_thr=nt, longest_segment=int(seg.max()),
+                classes_with_rows=int((seg > 0).sum()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--img", type=int, default=640)
@@ -171,7 +253,8 @@ def main():
     ev.conf_threshold = ev.cls_threshold = thr
     print(json.dumps({"heads": heads, "threshold": thr, "rows_per_image": rows, "grid": grid}), flush=True)
 
-    modes = {"host": lambda: host_pass(ev, batches), "device": lambda: device_pass(ev, batches, nc, dev)}
+    modes = {"host": lambda: host_pass(ev, batches), "device": lambda: device_pass(ev, batches, nc, dev),
+             "device_ap": lambda: device_ap_pass(ev, batches, nc, dev)}
     runs = {k: [] for k in modes}
     for rep in range(args.reps + 1):
         for k, fn in modes.items():
@@ -191,7 +274,16 @@ def main():
                   "n_pred": rs[0][2], "metrics": rs[0][3]}
         res[k]["img_per_s"] = args.batch * args.batches / res[k]["total_s"]
     res["metrics_equal"] = res["host"]["metrics"] == res["device"]["metrics"] and res["host"]["n_pred"] == res["device"]["n_pred"]
+    # the AP sum is added left to right on the device and pairwise by np.sum: the four figures agree to 1e-12, not to the bit —
+    # where no two rows of a class with different TP masks share a confidence ("table": how many rows of this pass do; among those
+    # the host's argsort is unstable and the device takes table order, and the device's curves are then held to the restatement)
+    res["device_ap_metrics_close"] = res["device_ap"]["n_pred"] == res["device"]["n_pred"] and bool(
+        np.allclose(res["device_ap"]["metrics"], res["device"]["metrics"], rtol=1e-12, atol=1e-12))
+    res["device_ap_metrics_max_abs_diff"] = float(np.abs(np.subtract(res["device_ap"]["metrics"], res["device"]["metrics"])).max())
+    res["table"] = restatement_check(ev, batches, nc, dev)
+    res["device_ap_no_slower"] = res["device_ap"]["total_s"] <= res["device"]["total_s"]
     res["yh_val_match"] = dict(ms_per_launch=k_ms, **k_info)
+    res["yh_val_ap"] = ap_kernel_ms(ev, batches, nc, dev)
     if args.out:
         with open(args.out, "w") as f:
             json.dump(res, f, indent=1)

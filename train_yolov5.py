@@ -263,7 +263,8 @@ class Training:
         model.eval()
         self.validate.yolo = model
         all_gts, all_preds = [], []
-        acc = MatchAccumulator(self.hyp['num_class'], self.device) if self.hyp.get('device_metric', False) else None
+        device_ap = bool(self.hyp.get('device_ap', False))
+        acc = MatchAccumulator(self.hyp['num_class'], self.device) if device_ap or self.hyp.get('device_metric', False) else None
         for x in self.val_dataloader:
             if acc is not None:
                 # the match table stays on the device.  The boxes go through the validation driver's frame change: the batch's
@@ -280,7 +281,11 @@ class Training:
                 gt = ann[b][ann[b][:, 4] >= 0][:, :5]
                 all_gts.append(gt)
                 all_preds.append(o.numpy() if o is not None else np.zeros((0, 6), np.float32))
-        if acc is not None:
+        if device_ap:
+            ap, precision, recall, npred, gt_hist = acc.finish_ap()      # AP and curves from the device (yh_val_ap): one copy
+            n_pred = int(npred.sum())
+            m, m50, mp, mr = mAP_v2.from_curves(ap, precision, recall, gt_hist).get_mean_metrics() if n_pred else (0., 0., 0., 0.)
+        elif acc is not None:
             conf, cls, tp, gt_hist = acc.finish()        # the one device-to-host copy of the pass
             n_pred = len(conf)
             m, m50, mp, mr = mAP_v2.from_matches(conf, cls, tp, gt_hist).get_mean_metrics() if n_pred else (0., 0., 0., 0.)
@@ -360,6 +365,8 @@ def main(argv=None, training_cls=None, default_cfg=None):
                     f"Default: {MULTI_SCALE_FREE_FRACTION:.0%} of the device memory free when training starts")
     ap.add_argument("--device-metric", action="store_true", help="the evaluation after an epoch matches its detections against the "
                     "ground truth on the GPU (yh_val_match) and copies one match table to the host at its end")
+    ap.add_argument("--device-ap", action="store_true", help="implies --device-metric; the AP and the precision / recall curves of that "
+                    "evaluation are computed on the GPU too (yh_val_ap): the per-class curves come back, not the match table")
     args = ap.parse_args(argv)
     if args.deterministic:                                               # before any model / program is built
         import yoloseries_amd
@@ -389,6 +396,7 @@ def main(argv=None, training_cls=None, default_cfg=None):
             ap.error("--augment and --device-letterbox are two ingest paths: the augmentation already runs on the device")
     if args.multi_scale: hyp['mutil_scale_training'] = True              # noqa: E701
     if args.device_metric: hyp['device_metric'] = True                   # noqa: E701
+    if args.device_ap: hyp['device_ap'] = hyp['device_metric'] = True    # noqa: E701
     if args.multi_scale_budget_gb is not None: hyp['multi_scale_budget_gb'] = args.multi_scale_budget_gb   # noqa: E701
     if training_cls is not None:                                         # train_yolox.py:808: Training(hyp)
         t = training_cls(hyp)

@@ -10,6 +10,8 @@
     letterbox runs on the GPU, raw_imgsize_collate_fn -> DeviceLetterboxPrefetcher).
   * --device-metric (hyp['device_metric']): the detections stay on the device — evaluate_matches un-letterboxes and matches them
     there (yh_val_match), a MatchAccumulator keeps the match tables, one copy at the end feeds mAP_v2.from_matches.  Same metric.
+  * --device-ap (hyp['device_ap'], implies device_metric): the AP and the precision / recall curves are computed on the device too
+    (yh_val_ap through MatchAccumulator.finish_ap); the per-class curves come back instead of the table, mAP_v2.from_curves reads them.
   Out of scope (SURVEY §8 "OUT OF SCOPE"): image dumps / plots, the auxiliary classifier, pickled box caches.
 
     python val_yolov5.py --img 640 --batch 16 --val-batches 4 [--ckpt checkpoints/yolov5_small_epoch_1.pth]
@@ -115,7 +117,8 @@ class Training:
         eval_model.eval()
         validater = self.build_evaluator(eval_model)
         all_preds, all_gts = [], []
-        acc = MatchAccumulator(self.hyp['num_class'], self.device) if self.hyp.get('device_metric', False) else None
+        device_ap = bool(self.hyp.get('device_ap', False))
+        acc = MatchAccumulator(self.hyp['num_class'], self.device) if device_ap or self.hyp.get('device_metric', False) else None
         t0 = time.time()
         n_img = 0
         for x in self.val_dataloader:
@@ -133,12 +136,16 @@ class Training:
                     all_preds.append(np.zeros((0, 6)))
                 all_gts.append(np.concatenate((gt_bbox[j], gt_cls[j][:, None]), axis=1))
             n_img += len(preds)
-        if acc is not None:
+        if device_ap:
+            ap, precision, recall, npred, gt_hist = acc.finish_ap()      # the curves instead of the table: still one copy
+        elif acc is not None:
             conf, cls, tp, gt_hist = acc.finish()        # the one device-to-host copy (and the only wait) of the pass
         torch.cuda.synchronize()
         dt = time.time() - t0
-        n_pred = len(conf) if acc is not None else int(sum(len(p) for p in all_preds))
-        if acc is not None and n_pred:
+        n_pred = int(npred.sum()) if device_ap else len(conf) if acc is not None else int(sum(len(p) for p in all_preds))
+        if device_ap and n_pred:
+            m, m50, mp, mr = mAP_v2.from_curves(ap, precision, recall, gt_hist, self.cwd / "result" / "curve").get_mean_metrics()
+        elif acc is not None and n_pred:
             m, m50, mp, mr = mAP_v2.from_matches(conf, cls, tp, gt_hist, self.cwd / "result" / "curve").get_mean_metrics()
         elif any(len(p) for p in all_preds):
             m, m50, mp, mr = mAP_v2(all_gts, all_preds, self.cwd / "result" / "curve").get_mean_metrics()
@@ -163,6 +170,8 @@ def main(argv=None, training_cls=None, default_cfg=None):
                     "(raw_imgsize_collate_fn + DeviceLetterboxPrefetcher; same batches, bit for bit)")
     ap.add_argument("--device-metric", action="store_true", help="un-letterbox and match the detections against the ground truth on the "
                     "GPU (yh_val_match): one match table crosses to the host at the end of the pass instead of every image's rows")
+    ap.add_argument("--device-ap", action="store_true", help="with the matching on the GPU (implies --device-metric), compute the AP and "
+                    "the precision / recall curves there too (yh_val_ap): the per-class curves cross to the host, not the match table")
     args = ap.parse_args(argv)
     hyp = Config().get_config(args.cfg)
     if args.img: hyp['input_img_size'] = [args.img, args.img]            # noqa: E701
@@ -172,6 +181,7 @@ def main(argv=None, training_cls=None, default_cfg=None):
     if args.ckpt: hyp['pretrained_model_path'] = args.ckpt               # noqa: E701
     if args.device_letterbox: hyp['device_letterbox'] = True             # noqa: E701
     if args.device_metric: hyp['device_metric'] = True                   # noqa: E701
+    if args.device_ap: hyp['device_ap'] = hyp['device_metric'] = True    # noqa: E701
     if training_cls is not None:
         v = training_cls(hyp)
     else:

@@ -235,6 +235,8 @@ _SIGS = {
     "yh_nms_batched": (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "yh_val_match": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_double), _i32,
                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "yh_val_ap_ws_bytes": (_sz, [_i32, _i32]),
+    "yh_val_ap": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 

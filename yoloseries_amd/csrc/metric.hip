@@ -163,3 +163,202 @@ extern "C" int yh_val_match(const float* det, const int32_t* nkeep, const float*
     YH_CHECK_LAUNCH("yh_val_match");
     return YH_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- yh_val_ap
+// The rest of the metric: the match table of a whole pass (conf, cls, tp as MatchAccumulator holds them) to the per-class AP and the
+// precision / recall curves of utils/mAP.py compute_ap_per_class / compute_ap, so that a pass returns num_class * (n_thr + 2 * n_pr)
+// doubles instead of the table.  The rows come ordered (`order`: class ascending, then conf descending; the caller sorts).
+//
+// Operation order, every operation a correctly rounded fp64 operation, once.  Class c with T = gt_hist[c] > 0 and n > 0 rows, row i
+// of its segment (0-based), threshold k:
+//   ctp_i = rows <= i with bit k set (integer)      rec_i = (double)ctp_i / ((double)T + 1e-16)
+//   pre_i = (double)ctp_i / ((double)(i + 1) + 1e-16)                          (ctp_i + cfp_i is the integer i + 1)
+//   AP      rec' = [0, rec.., 1], pre' = [1, pre.., 0], env_j = max over m >= j of pre'_m, ys_q = interp(xs_ap[q]; rec', env),
+//           ap = sum over q of ((ys_{q+1} + ys_q) / 2) * (xs_ap[q+1] - xs_ap[q]), added left to right from q = 0
+//   curves  (threshold 0)  recall[q] = interp(-xs_pr[q]; -(double)conf, rec, left = 0), precision[q] likewise with pre, left = 1
+//   interp  NumPy's: x < xp[0] -> left (default fp[0]); x > xp[last] -> fp[last]; else j = the last index with xp[j] <= x and the
+//           result is fp[j] if x == xp[j], else ((fp[j+1] - fp[j]) / (xp[j+1] - xp[j])) * (x - xp[j]) + fp[j]
+// Outside the contract: two rows of one class with equal conf and different tp masks (the host's order there comes from an unstable
+// sort; with the stable sort of MatchAccumulator.finish_ap the lower original row comes first), NaN or negative conf, a grid that is
+// not ascending, a class with more true positives than ground truth (rec' would not be sorted).  None of them can make the kernel
+// read or write out of bounds: every index into a table is bounded by construction and an entry of `order` is clamped to [0, N).
+//
+// One workgroup of four waves per (class, threshold).  Two lanes find the class's segment by binary search in cls[order[.]].  The
+// segment is walked forward VA_CHUNK rows at a time: a ballot and a popcount are the wave's inclusive scan of bit k, the waves'
+// totals and the chunks' carry go through LDS, ctp goes to the workspace ([n_thr][N] int32).  rec' / pre' are then walked backward
+// in chunks for the envelope (a shuffle suffix-max per wave, the carry from the chunks behind); rec' is non-decreasing, so index j
+// answers exactly the grid points in [rec'_j, rec'_{j+1}): the lane that holds j looks them up in the grid (LDS) and writes their
+// ys, no envelope is stored.  The k = 0 workgroup also writes the two curves, a binary search in the segment's conf per grid point.
+#define VA_THREADS 256
+#define VA_CHUNK 256                        // rows per step of either walk: one per thread
+#define VA_MAX_AP 1024                      // n_ap at most: the grid and its ys live in LDS (16 KiB)
+
+__device__ __forceinline__ int va_row(const int32_t* __restrict__ order, int i, int N) { return min(max(order[i], 0), N - 1); }
+
+// the inner branch of NumPy's interp: (slope) * (x - x0) + f0, three roundings and a division, never fused
+__device__ __forceinline__ double va_lerp(double f0, double f1, double x0, double x1, double x)
+{
+    return __dadd_rn(__dmul_rn(__ddiv_rn(__dsub_rn(f1, f0), __dsub_rn(x1, x0)), __dsub_rn(x, x0)), f0);
+}
+
+__global__ __launch_bounds__(VA_THREADS) void val_ap_kernel(
+    const float* __restrict__ conf, const int32_t* __restrict__ cls, const uint16_t* __restrict__ tp, const int32_t* __restrict__ order,
+    int N, const int32_t* __restrict__ gt_hist, int n_thr, const double* __restrict__ xs_ap, int n_ap, const double* __restrict__ xs_pr,
+    int n_pr, int32_t* ctp_ws, double* __restrict__ ap, double* __restrict__ precision, double* __restrict__ recall,
+    int32_t* __restrict__ npred)
+{
+    __shared__ double s_xs[VA_MAX_AP], s_ys[VA_MAX_AP];
+    __shared__ double s_env[VA_CHUNK + 1], s_rec[VA_CHUNK + 1];       // [VA_CHUNK]: the first element of the chunk behind
+    __shared__ double s_wmax[VA_THREADS / 64];
+    __shared__ int s_wsum[VA_THREADS / 64];
+    __shared__ int s_seg[2];
+    const int c = blockIdx.x, k = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+
+    if (t < 2) {                                                      // the first row of class c (t = 0) and of class c + 1 (t = 1)
+        int lo = 0, hi = N;
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (cls[va_row(order, mid, N)] < c + t) lo = mid + 1; else hi = mid;
+        }
+        s_seg[t] = lo;
+    }
+    __syncthreads();
+    const int s = s_seg[0], n = s_seg[1] - s_seg[0];
+    const int T = gt_hist[c];
+    if (k == 0 && t == 0) npred[c] = max(n, 0);
+    if (n <= 0 || T <= 0) {                                           // uniform: nothing to rank, or nothing to find
+        if (t == 0) ap[(long)c * n_thr + k] = 0.0;
+        if (k == 0)
+            for (int q = t; q < n_pr; q += VA_THREADS) precision[(long)c * n_pr + q] = recall[(long)c * n_pr + q] = 0.0;
+        return;
+    }
+    const double t_den = __dadd_rn((double)T, 1e-16);
+
+    // ---- forward: ctp of every row of the segment
+    int32_t* ctp = ctp_ws + (long)k * N + s;
+    int carry = 0;
+    for (int base = 0; base < n; base += VA_CHUNK) {
+        const int i = base + t;
+        const int bit = i < n ? (tp[va_row(order, s + i, N)] >> k) & 1 : 0;
+        const unsigned long long m = __ballot(bit);
+        const int incl = __popcll(m & (~0ull >> (63 - lane)));
+        if (lane == 63) s_wsum[wave] = incl;
+        __syncthreads();
+        int before = carry;
+        for (int w = 0; w < VA_THREADS / 64; ++w) {
+            if (w < wave) before += s_wsum[w];
+            carry += s_wsum[w];
+        }
+        if (i < n) ctp[i] = before + incl;
+        __syncthreads();                                              // the totals have been read; after the last chunk: ctp is written
+    }
+
+    // ---- the curves, threshold 0: one grid point per thread, a binary search in the segment's conf
+    if (k == 0)
+        for (int q = t; q < n_pr; q += VA_THREADS) {
+            const double x = -xs_pr[q];
+            const double x_first = -(double)conf[va_row(order, s, N)], x_last = -(double)conf[va_row(order, s + n - 1, N)];
+            double r, p;
+            if (x < x_first) {
+                r = 0.0; p = 1.0;
+            } else {
+                int j = n - 1;
+                if (!(x > x_last)) {                                  // the last j with xp[j] <= x
+                    int lo = 0, hi = n;
+                    while (lo < hi) {
+                        const int mid = lo + ((hi - lo) >> 1);
+                        if (-(double)conf[va_row(order, s + mid, N)] <= x) lo = mid + 1; else hi = mid;
+                    }
+                    j = max(lo - 1, 0);
+                }
+                const double xj = -(double)conf[va_row(order, s + j, N)];
+                const double cj = (double)ctp[j];
+                r = __ddiv_rn(cj, t_den);
+                p = __ddiv_rn(cj, __dadd_rn((double)(j + 1), 1e-16));
+                if (j < n - 1 && xj != x) {
+                    const double xn = -(double)conf[va_row(order, s + j + 1, N)], cn = (double)ctp[j + 1];
+                    r = va_lerp(r, __ddiv_rn(cn, t_den), xj, xn, x);
+                    p = va_lerp(p, __ddiv_rn(cn, __dadd_rn((double)(j + 2), 1e-16)), xj, xn, x);
+                }
+            }
+            recall[(long)c * n_pr + q] = r;
+            precision[(long)c * n_pr + q] = p;
+        }
+
+    // ---- backward over rec' / pre' (L = n + 2 elements): the envelope, and the ys of the grid points each index answers
+    for (int q = t; q < n_ap; q += VA_THREADS) {
+        s_xs[q] = xs_ap[q];
+        s_ys[q] = 0.0;                                                // x >= 1 = rec'[L - 1]: env[L - 1] = 0
+    }
+    __syncthreads();
+    const int L = n + 2;
+    double env_behind = 0.0, rec_behind = 1.0;                        // pre' >= 0 and ends in 0: 0 is the neutral element here
+    for (int base = (L - 1) / VA_CHUNK * VA_CHUNK; base >= 0; base -= VA_CHUNK) {
+        const int j = base + t;
+        double r = 1.0, v = 0.0;                                      // j == L - 1, and the idle lanes behind it
+        if (j == 0) {
+            r = 0.0; v = 1.0;
+        } else if (j < L - 1) {
+            const double cj = (double)ctp[j - 1];
+            r = __ddiv_rn(cj, t_den);
+            v = __ddiv_rn(cj, __dadd_rn((double)j, 1e-16));
+        }
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const double o = __shfl_down(v, off);
+            if (lane + off < 64) v = fmax(v, o);
+        }
+        if (lane == 0) s_wmax[wave] = v;
+        __syncthreads();
+        double behind = env_behind;
+        for (int w = VA_THREADS / 64 - 1; w > wave; --w) behind = fmax(behind, s_wmax[w]);
+        v = fmax(v, behind);
+        s_env[t] = v;
+        s_rec[t] = r;
+        if (t == 0) { s_env[VA_CHUNK] = env_behind; s_rec[VA_CHUNK] = rec_behind; }
+        __syncthreads();
+        const double r1 = s_rec[t + 1];
+        if (j < L - 1 && r < r1) {                                    // grid points in [rec'_j, rec'_{j+1}): j is their last index
+            const double v1 = s_env[t + 1];
+            int lo = 0, hi = n_ap;
+            while (lo < hi) {                                         // the first grid point >= rec'_j
+                const int mid = (lo + hi) >> 1;
+                if (s_xs[mid] < r) lo = mid + 1; else hi = mid;
+            }
+            for (int q = lo; q < n_ap && s_xs[q] < r1; ++q) s_ys[q] = s_xs[q] == r ? v : va_lerp(v, v1, r, r1, s_xs[q]);
+        }
+        env_behind = s_env[0];
+        rec_behind = s_rec[0];
+        __syncthreads();                                              // the chunk has been read (and, at the end, ys is written)
+    }
+    for (int q = t; q < n_ap && s_xs[q] < 0.0; q += VA_THREADS) s_ys[q] = env_behind;      // below rec'[0] = 0: left = env[0]
+    __syncthreads();
+    if (t == 0) {
+        double sum = 0.0;
+        for (int q = 0; q + 1 < n_ap; ++q)
+            sum = __dadd_rn(sum, __dmul_rn(__ddiv_rn(__dadd_rn(s_ys[q + 1], s_ys[q]), 2.0), __dsub_rn(s_xs[q + 1], s_xs[q])));
+        ap[(long)c * n_thr + k] = sum;
+    }
+}
+
+extern "C" size_t yh_val_ap_ws_bytes(int N, int n_thr) { return N > 0 && n_thr > 0 ? (size_t)N * (size_t)n_thr * sizeof(int32_t) : 0; }
+
+extern "C" int yh_val_ap(const float* conf, const int32_t* cls, const uint16_t* tp, const int32_t* order, int N, const int32_t* gt_hist,
+                         int num_class, int n_thr, const double* xs_ap, int n_ap, const double* xs_pr, int n_pr, double* ap,
+                         double* precision, double* recall, int32_t* npred, void* ws, yh_stream stream)
+{
+    YH_CHECK_ARG(conf && cls && tp && order && gt_hist && xs_ap && xs_pr, "yh_val_ap: null input pointer");
+    YH_CHECK_ARG(ap && precision && recall && npred && ws, "yh_val_ap: null output or ws pointer");
+    YH_CHECK_ARG(N > 0 && num_class > 0, "yh_val_ap: N and num_class must be positive (N=%d num_class=%d)", N, num_class);
+    YH_CHECK_ARG(n_thr >= 1 && n_thr <= VM_MAX_THR, "yh_val_ap: n_thr=%d is outside 1..%d", n_thr, VM_MAX_THR);
+    YH_CHECK_ARG(n_ap >= 2 && n_ap <= VA_MAX_AP, "yh_val_ap: n_ap=%d is outside 2..%d", n_ap, VA_MAX_AP);
+    YH_CHECK_ARG(n_pr >= 1, "yh_val_ap: n_pr=%d must be positive", n_pr);
+    YH_CHECK_ARG(((((uintptr_t)conf) | ((uintptr_t)cls) | ((uintptr_t)order) | ((uintptr_t)gt_hist) | ((uintptr_t)npred) | ((uintptr_t)ws)) & 3) == 0 &&
+                 (((uintptr_t)tp) & 1) == 0 &&
+                 ((((uintptr_t)xs_ap) | ((uintptr_t)xs_pr) | ((uintptr_t)ap) | ((uintptr_t)precision) | ((uintptr_t)recall)) & 7) == 0,
+                 "yh_val_ap: unaligned table (conf, cls, order, gt_hist, npred, ws 4 bytes; tp 2 bytes; the double tables 8 bytes)");
+    hipLaunchKernelGGL(val_ap_kernel, dim3(num_class, n_thr), dim3(VA_THREADS), 0, (hipStream_t)stream,
+                       conf, cls, tp, order, N, gt_hist, n_thr, xs_ap, n_ap, xs_pr, n_pr, (int32_t*)ws, ap, precision, recall, npred);
+    YH_CHECK_LAUNCH("yh_val_ap");
+    return YH_OK;
+}

@@ -30,6 +30,7 @@ def _decode_ws(owner, d, dev):
     return ws.data_ptr()
 
 IOU_THRESHOLDS = tuple(np.linspace(0.5, 0.95, 10).tolist())        # mAP_v2.iou_thr
+AP_GRID, PR_GRID = 101, 1000                                        # compute_ap's recall grid, compute_ap_per_class's confidence grid
 
 
 def info_tensor(info):
@@ -42,7 +43,7 @@ def info_tensor(info):
 
 
 class MatchAccumulator:
-    """The match tables of a validation pass, kept on the device: append(evaluate_matches(...)) per batch, finish() once.  Owns the
+    """The match tables of a validation pass, kept on the device: append(evaluate_matches(...)) per batch, finish() or finish_ap() once.  Owns the
     gt_hist buffer that yh_val_match accumulates into (pass acc.gt_hist to evaluate_matches)."""
 
     def __init__(self, num_class, device):
@@ -57,14 +58,22 @@ class MatchAccumulator:
         self._parts.append((m['conf'], m['cls'], m['tp'], m['nrow']))
         self.images += m['nrow'].numel()
 
+    def _compact(self):
+        """-> (conf, cls int32, tp int16) of the rows that count, on the device; None without a batch"""
+        if not self._parts:
+            return None
+        keep = torch.cat([(torch.arange(c.shape[1], device=c.device)[None, :] < n[:, None]).reshape(-1) for c, _, _, n in self._parts])
+        conf = torch.cat([c.reshape(-1) for c, _, _, _ in self._parts])[keep]
+        cls = torch.cat([c.reshape(-1) for _, c, _, _ in self._parts])[keep]
+        tp = torch.cat([t.reshape(-1) for _, _, t, _ in self._parts])[keep]
+        return conf, cls, tp
+
     def finish(self):
         """-> (conf (N,) float32, cls (N,) int32, tp (N, 10) bool, gt_hist (num_class,) int64) as NumPy, the padded rows compacted
         away on the device and everything brought over in ONE device-to-host copy (the only point the host waits)"""
-        if self._parts:
-            keep = torch.cat([(torch.arange(c.shape[1], device=c.device)[None, :] < n[:, None]).reshape(-1) for c, _, _, n in self._parts])
-            conf = torch.cat([c.reshape(-1) for c, _, _, _ in self._parts])[keep]
-            cls = torch.cat([c.reshape(-1) for _, c, _, _ in self._parts])[keep]
-            tp = torch.cat([t.reshape(-1) for _, _, t, _ in self._parts])[keep]
+        rows = self._compact()
+        if rows is not None:
+            conf, cls, tp = rows
             flat = torch.cat([conf.view(torch.int32), cls, tp.to(torch.int32) & 0xffff, self.gt_hist])
         else:
             flat = self.gt_hist
@@ -73,6 +82,37 @@ class MatchAccumulator:
         conf, cls, bits, hist = h[:n].view(np.float32), h[n:2 * n], h[2 * n:3 * n], h[3 * n:]
         tp = ((bits[:, None] >> np.arange(len(IOU_THRESHOLDS))[None, :]) & 1).astype(bool)
         return conf.copy(), cls.copy(), tp, hist.astype(np.int64)
+
+    def finish_ap(self):
+        """The AP and the precision / recall curves of the pass, computed on the device (yh_val_ap) -> (ap (num_class, 10),
+        precision (num_class, 1000), recall (num_class, 1000), npred (num_class,) int64, gt_hist (num_class,) int64) as NumPy, for
+        mAP_v2.from_curves: what compute_ap_per_class makes of finish()'s table, with a row per class id (zeros where the class has
+        no ground truth or no detection).  The rows are compacted as in finish(), ordered by one stable sort of an int64 key (class
+        in the high word, the complement of conf's bits in the low one: class ascending, conf descending, ties in table order) and
+        ONE copy brings the five results over.  Without any detection nothing is launched: ap, precision and recall have no rows."""
+        nc, nt = self.num_class, len(IOU_THRESHOLDS)
+        rows = self._compact()
+        if rows is None or rows[0].numel() == 0:
+            return (np.zeros((0, nt)), np.zeros((0, PR_GRID)), np.zeros((0, PR_GRID)), np.zeros(nc, np.int64),
+                    self.gt_hist.cpu().numpy().astype(np.int64))
+        conf, cls, tp = (t.contiguous() for t in rows)
+        n, dev = conf.numel(), conf.device
+        key = (cls.to(torch.int64) << 32) | (0xFFFFFFFF - (conf.view(torch.int32).to(torch.int64) & 0xFFFFFFFF))
+        order = torch.sort(key, stable=True)[1].to(torch.int32)
+        xs = torch.from_numpy(np.concatenate((np.linspace(0, 1, AP_GRID), np.linspace(0, 1, PR_GRID)))).to(dev)
+        nd = nc * (nt + 2 * PR_GRID)
+        out = torch.empty(nd + nc, dtype=torch.float64, device=dev)           # the doubles, then npred and gt_hist as int32 pairs
+        tail = out[nd:].view(torch.int32)
+        ws = torch.empty(max(int(lib().yh_val_ap_ws_bytes(n, nt)), 16), dtype=torch.uint8, device=dev)
+        o_ap, o_pre, o_rec = out[:nc * nt], out[nc * nt:nc * (nt + PR_GRID)], out[nc * (nt + PR_GRID):nd]
+        check(lib().yh_val_ap(conf.data_ptr(), cls.data_ptr(), tp.data_ptr(), order.data_ptr(), n, self.gt_hist.data_ptr(), nc, nt,
+                              xs.data_ptr(), AP_GRID, xs[AP_GRID:].data_ptr(), PR_GRID, o_ap.data_ptr(), o_pre.data_ptr(),
+                              o_rec.data_ptr(), tail.data_ptr(), ws.data_ptr(), _lib.stream_ptr()), "yh_val_ap")
+        tail[nc:] = self.gt_hist
+        h = out.cpu().numpy()
+        ints = h[nd:].view(np.int32).astype(np.int64)
+        return (h[:nc * nt].reshape(nc, nt).copy(), h[nc * nt:nc * (nt + PR_GRID)].reshape(nc, PR_GRID).copy(),
+                h[nc * (nt + PR_GRID):nd].reshape(nc, PR_GRID).copy(), ints[:nc], ints[nc:])
 
 
 class YOLOV5Evaluator:

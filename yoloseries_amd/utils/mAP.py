@@ -40,6 +40,23 @@ class mAP_v2:
         self.save_dir = plot_save_dir
         self.type = type
         self._tables = None
+        self._curves = None
+
+    @classmethod
+    def from_curves(cls, ap, precision, recall, gt_hist, plot_save_dir=None, type='coco'):
+        """The metric from per-class curves instead of a match table (yh_val_ap through MatchAccumulator.finish_ap()): ap
+        (num_class, 10), precision and recall (num_class, 1000) with a row per class id — what compute_ap_per_class builds per
+        class — and gt_hist.  The classes with ground truth are picked and the tail of compute_ap_per_class runs on them.  With no
+        row at all (a pass without a detection) every class's curves are zeros."""
+        self = cls([], [], plot_save_dir, type)
+        ap, precision, recall, gt_hist = (np.asarray(a) for a in (ap, precision, recall, gt_hist))
+        assert gt_hist.ndim == 1 and ap.ndim == precision.ndim == recall.ndim == 2 and len(ap) == len(precision) == len(recall)
+        tot_cls = np.nonzero(gt_hist)[0]
+        if len(ap) == 0:
+            ap, precision, recall = (np.zeros((len(gt_hist), a.shape[1])) for a in (ap, precision, recall))
+        assert len(ap) == len(gt_hist)
+        self._curves = (ap[tot_cls], precision[tot_cls], recall[tot_cls], tot_cls)
+        return self
 
     @classmethod
     def from_matches(cls, conf, pcls, tp, gt_hist, plot_save_dir=None, type='coco'):
@@ -93,6 +110,8 @@ class mAP_v2:
         return tps, pred_all[:, 4], pred_all[:, 5], tot_cls, np.array([(tcls == c).sum() for c in tot_cls], dtype=np.int64)
 
     def compute_ap_per_class(self):
+        if self._curves is not None:
+            return self._summary(*self._curves)
         tps, conf, pcls, tot_cls, num_tars = self.match_tables()
         sort_i = np.argsort(conf)[::-1]
         stp, scof, scls = tps[sort_i], conf[sort_i], pcls[sort_i]
@@ -112,6 +131,11 @@ class mAP_v2:
                 precision[i] = np.interp(-xs, -scof[mi], cpre[:, 0], left=1)
                 for j in range(stp.shape[1]):
                     ap[i, j], _, _ = self.compute_ap(crec[:, j], cpre[:, j], self.type)
+        return self._summary(ap, precision, recall, tot_cls)
+
+    @staticmethod
+    def _summary(ap, precision, recall, tot_cls):
+        """the tail both constructors share: F1, the confidence that maximises its smoothed mean, the curves read there"""
         f1 = 2 * precision * recall / (precision + recall + 1e-16)
         best_i = smooth(f1.mean(0), 0.1).argmax()
         return {"precision": precision[:, best_i], "recall": recall[:, best_i], "ap": ap, "f1": f1[:, best_i], "unique_cls": tot_cls}
