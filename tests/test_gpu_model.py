@@ -549,28 +549,22 @@ def test_step_deterministic_parts_bit_identical_at_judged_shape(dev, name):
             assert not bad, f"pass {r}: tensors {bad[:6]} of {len(cur)} differ from the first pass (0..{len(flat) - 1} outputs, {len(flat)} loss, then BatchNorm gradients)"
 
 
-@pytest.mark.parametrize("key", ["v5s_frozen", "yolox_frozen", "v5l_frozen"])
-def test_full_graph_gradients_eval_mode_bn(dev, key):
-    """A WELL-CONDITIONED check of the whole backward graph: the model in evaluation mode under autograd (BatchNorm on its
-    running statistics: no batch coupling, so bf16 rounding is not amplified through ~60 batch normalisations) against the
-    reference's gradients (g12_round3.npz).  Every parameter: gradient norm within 2 %, 256 sampled elements within
-    3e-2 of the parameter's largest gradient element — a mis-scaled branch of a concat / upsample / residual / stacked GEMM
-    gradient (5-10 %) cannot pass.  Under both backward schedules."""
-    from yoloseries_amd import models
-    g = np.load(os.path.join(G, "g14_round5.npz" if key == "v5l_frozen" else "g12_round3.npz"))
+def _frozen_bn_gradients(dev, fixture, key, make, xseed, xshape, outs_of, norm_bar=None):
+    """The body of test_full_graph_gradients_eval_mode_bn for one key of a `_frozen_bwd` fixture (tools/gen_golden.py): `make()` in
+    evaluation mode under autograd on the fixture's state, input RandomState(xseed).rand(*xshape), under both backward schedules.
+    Output samples within 3e-2; EVERY parameter's sampled gradient elements and gradient norm within the bars below; running
+    statistics bit-unchanged.  `norm_bar`: {parameter name: floor of its norm bar} for the few NAMED parameters of a key whose bar
+    is wider than the rule, each with its measured figures at the caller.  Returns the model (its programs tell a caller which
+    kernels ran)."""
+    g = np.load(os.path.join(G, fixture))
     seed = int(g[f"{key}_seed"][0])
-    if key == "v5s_frozen":
-        model, xs, outs_of = models.YOLOV5Small(3, 80), 1201, (lambda o: list(o))
-    elif key == "v5l_frozen":            # config #4's model (g14, round 5): 499 parameters, 96 sampled elements each
-        model, xs, outs_of = models.YOLOV5Large(3, 80), 1401, (lambda o: list(o))
-    else:
-        model, xs, outs_of = models.YOLOXSmall(1, 3, 80, 0.01), 1202, (lambda o: list(o.values()))
+    model = make()
     fill_state(model, seed)
     rm0 = {n: b.clone() for n, b in model.named_buffers()}
     model = model.to(dev).eval()
     names = [n for n, _ in model.named_parameters()]
     assert names == [str(n) for n in g[f"{key}_pnames"]]
-    x = np.random.RandomState(xs).rand(2, 3, 256, 256).astype(np.float32)
+    x = np.random.RandomState(xseed).rand(*xshape).astype(np.float32)
     for streams in (1, 0):
         outs = outs_of(model(torch.from_numpy(x).to(dev)))
         for prog in model._yh_state()['progs'].values():
@@ -583,7 +577,8 @@ def test_full_graph_gradients_eval_mode_bn(dev, key):
             flat = o.detach().float().contiguous().cpu().numpy().reshape(-1)
             _close(flat[g[f"{key}_out_idx{i}"]], g[f"{key}_out_val{i}"], 3e-2, f"{key} eval-mode out{i}")
         grads = torch.autograd.grad(outs, list(model.parameters()), gos)
-        worst, bad = {}, []
+        assert len(grads) == len(names) == len(g[f"{key}_psig"])
+        worst, worst_n, bad = {}, {}, []
         for pi, (n, gr) in enumerate(zip(names, grads)):
             gf = gr.double().reshape(-1).cpu().numpy()
             s_sum, s_abs, s_norm, s_size, s_max = g[f"{key}_psig"][pi]
@@ -600,14 +595,37 @@ def test_full_graph_gradients_eval_mode_bn(dev, key):
                 tol_e, tol_n = max(8e-2, 2.0 * cal_e), max(5e-2, 2.0 * cal_n)
             elif key == "v5l_frozen":             # twice the depth of YOLOv5s in front of the 8 x 8 stage (128 pixels per weight-gradient sum): its
                 tol_n = max(2.5e-2, 2.0 * cal_n)  # 512 -> 512 bottleneck conv, the parameter the reference's own bf16 run is furthest off on (1.1 %), sits at 2.2 %
+            if norm_bar and n in norm_bar:
+                tol_n = max(norm_bar[n], tol_n)
             worst[kind] = max(worst.get(kind, 0.0), err / (s_max + 1e-30))
-            if err > tol_e * s_max + 1e-7 or abs(nrm - s_norm) > tol_n * s_norm + 1e-7:
+            worst_n[kind] = max(worst_n.get(kind, 0.0), abs(nrm - s_norm) / (s_norm + 1e-30))
+            if not (err <= tol_e * s_max + 1e-7 and abs(nrm - s_norm) <= tol_n * s_norm + 1e-7):       # (a NaN is off too)
                 bad.append((n, round(err / (s_max + 1e-30), 4), round(abs(nrm - s_norm) / (s_norm + 1e-30), 4)))
-        print(f"{key} streams={streams}: worst sampled error / largest element {worst}")
+        fmt = lambda d: ", ".join(f"{k} {v:.4f}" for k, v in sorted(d.items()))      # noqa: E731
+        print(f"{key} streams={streams}: worst sampled error / largest element: {fmt(worst)}; worst norm error: {fmt(worst_n)}")
         assert not bad, f"{key}: {len(bad)} of {len(names)} parameter gradients off (name, element error, norm error): {bad[:8]}"
     # evaluation mode: the running statistics did not move
     for n, b in model.named_buffers():
         assert torch.equal(b.cpu(), rm0[n]), n
+    return model
+
+
+@pytest.mark.parametrize("key", ["v5s_frozen", "yolox_frozen", "v5l_frozen"])
+def test_full_graph_gradients_eval_mode_bn(dev, key):
+    """A WELL-CONDITIONED check of the whole backward graph: the model in evaluation mode under autograd (BatchNorm on its
+    running statistics: no batch coupling, so bf16 rounding is not amplified through ~60 batch normalisations) against the
+    reference's gradients (g12_round3.npz).  Every parameter: gradient norm within 2 %, 256 sampled elements within
+    3e-2 of the parameter's largest gradient element — a mis-scaled branch of a concat / upsample / residual / stacked GEMM
+    gradient (5-10 %) cannot pass.  Under both backward schedules.  (tests/test_gpu_model_shapes.py: the same check off the square.)"""
+    from yoloseries_amd import models
+    fixture = "g14_round5.npz" if key == "v5l_frozen" else "g12_round3.npz"
+    if key == "v5s_frozen":
+        make, xs, outs_of = (lambda: models.YOLOV5Small(3, 80)), 1201, (lambda o: list(o))
+    elif key == "v5l_frozen":            # config #4's model (g14, round 5): 499 parameters, 96 sampled elements each
+        make, xs, outs_of = (lambda: models.YOLOV5Large(3, 80)), 1401, (lambda o: list(o))
+    else:
+        make, xs, outs_of = (lambda: models.YOLOXSmall(1, 3, 80, 0.01)), 1202, (lambda o: list(o.values()))
+    _frozen_bn_gradients(dev, fixture, key, make, xs, (2, 3, 256, 256), outs_of)
 
 
 def test_forward_fuse_deployment_flow(dev):

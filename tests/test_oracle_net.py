@@ -5,7 +5,10 @@ CPU, against the committed golden vectors (tools/gen_golden.py ran /root/referen
   * g6_blocks.npz   ConvBnAct / BasicBottleneck / C3 / FastSPP: eval output, train output, input gradient, the reference's
                     signature (sum | abs-sum | norm | first elements) of every parameter gradient, BN running statistics;
   * g7_model.npz    YOLOv5s: eval forward at 64^2, train forward at 256^2 (sampled), running statistics;
-  * g11_round2.npz  YOLOv5 m / l / x: eval forward at 64^2 on a RandomState-filled state, train forward at 256^2.
+  * g11_round2.npz  YOLOv5 m / l / x: eval forward at 64^2 on a RandomState-filled state, train forward at 256^2;
+  * g12_round3.npz  YOLOv5s: evaluation-mode BatchNorm under autograd, outputs and the gradient of every parameter at 256^2;
+  * g18_shapes*.npz the same for YOLOv5 s / m / x OFF THE SQUARE (3 x 96 x 160, 1 x 224 x 288, 2 x 416 x 416: H != W, odd maps,
+                    a deepest map smaller than the pool window, batch 1), and the YOLOv5s training forward at those shapes.
 
 fp32 on both sides (same torch build): 2e-5 relative to the tensor's largest value.
 """
@@ -142,3 +145,59 @@ def test_oracle_v5s_eval_mode_gradients_vs_reference():
         assert gf.size == int(s_size)
         assert abs(np.sqrt((gf ** 2).sum()) - s_norm) <= 1e-4 * s_norm + 1e-9, n
         assert np.abs(gf[g["v5s_frozen_pidx"][pi]] - g["v5s_frozen_pval"][pi]).max() <= 1e-4 * s_max + 1e-9, n
+
+
+G18 = {  # the v5* keys of tools/gen_golden.py::gen_g18: (fixture, model)
+    "v5s_96x160": ("g18_shapes.npz", "s"), "v5s_224x288": ("g18_shapes.npz", "s"), "v5s_416": ("g18_shapes.npz", "s"),
+    "v5m_96x160": ("g18_shapes_b.npz", "m"), "v5x_224x288": ("g18_shapes_b.npz", "x"),
+}
+
+
+@pytest.mark.parametrize("key", list(G18))
+def test_oracle_eval_mode_gradients_off_square_vs_reference(key):
+    """the g12 check at non-square inputs, odd maps and batch 1 / 3: pins the net oracle to the reference there, so that later
+    work can lean on the oracle at such shapes without a fixture.  Outputs and, per parameter, gradient norm and 64 sampled
+    elements; the tolerances of the g12 test above."""
+    fixture, name = G18[key]
+    g = np.load(os.path.join(G, fixture))
+    seed = int(g[f"{key}_seed"][0])
+    m = _model_cls(name)(3, 80)
+    fill_state(m, seed)
+    net = V5NetOracle(m.state_dict(), train=False, grad=True)
+    xshape = tuple(int(v) for v in g[f"{key}_xshape"])
+    assert xshape[2] % 32 == 0 and xshape[3] % 32 == 0
+    x = torch.from_numpy(np.random.RandomState(int(g[f"{key}_xseed"][0])).rand(*xshape).astype(np.float32))
+    outs = net(x)
+    r = np.random.RandomState(seed + 1)
+    gos = [torch.from_numpy((r.randn(*o.shape) * 0.1).astype(np.float32)) for o in outs]
+    for i, o in enumerate(outs):
+        assert tuple(o.shape) == tuple(g[f"{key}_out_shape{i}"]) == (xshape[0], 255, xshape[2] // (8 << i), xshape[3] // (8 << i))
+        _near(o.detach().reshape(-1).numpy()[g[f"{key}_out_idx{i}"]], g[f"{key}_out_val{i}"], f"{key} eval-mode out{i}")
+    names = [str(n) for n in g[f"{key}_pnames"]]
+    assert names == [n for n, _ in m.named_parameters()]
+    grads = torch.autograd.grad(outs, [net.params[n] for n in names], gos)
+    for pi, (n, gr) in enumerate(zip(names, grads)):
+        gf = gr.double().reshape(-1).numpy()
+        s_sum, s_abs, s_norm, s_size, s_max = g[f"{key}_psig"][pi]
+        assert gf.size == int(s_size)
+        assert abs(np.sqrt((gf ** 2).sum()) - s_norm) <= 1e-4 * s_norm + 1e-9, n
+        assert np.abs(gf[g[f"{key}_pidx"][pi]] - g[f"{key}_pval"][pi]).max() <= 1e-4 * s_max + 1e-9, n
+
+
+@pytest.mark.parametrize("key", [k for k in G18 if k.startswith("v5s_")])
+def test_oracle_v5s_train_forward_off_square_vs_reference(key):
+    """one training-mode forward on the seeded default init: sampled head outputs and the running statistics of four layers,
+    at the tolerances of the YOLOv5s / m / l / x tests above"""
+    g = np.load(os.path.join(G, G18[key][0]))
+    torch.manual_seed(0)
+    net = V5NetOracle(_model_cls("s")(3, 80).state_dict(), train=True)
+    xshape = tuple(int(v) for v in g[f"{key}_xshape"])
+    x = torch.from_numpy(np.random.RandomState(int(g[f"{key}_xseed"][0])).rand(*xshape).astype(np.float32))
+    with torch.no_grad():
+        outs = net(x)
+    for i, o in enumerate(outs):
+        assert tuple(o.shape) == tuple(g[f"{key}_train_shape{i}"])
+        _near(o.reshape(-1).numpy()[g[f"{key}_train_idx{i}"]], g[f"{key}_train_val{i}"], f"{key} train out{i}", 2e-4)
+    for pn, tol in (("focus", 1e-5), ("backbone_stage2_conv", 1e-4), ("backbone_stage4_conv", 1e-4), ("head_stage4_bscp.cba3", 5e-4)):
+        _near(net.sd[pn + ".bn.running_mean"].numpy(), g[f"{key}_rm_{pn}"], f"{key} {pn} running_mean", tol)
+        _near(net.sd[pn + ".bn.running_var"].numpy(), g[f"{key}_rv_{pn}"], f"{key} {pn} running_var", tol)

@@ -95,6 +95,9 @@ def main():
     if sys.argv[1:] == ["--only", "g15"]:
         gen_g15(ref_loss)
         return
+    if sys.argv[1:] == ["--only", "g18"]:
+        gen_g18(ref_models)
+        return
     from yoloseries_amd.utils.synth import COCO_ANCHORS, synth_head_outputs, synth_targets
 
     os.makedirs(OUT, exist_ok=True)
@@ -554,10 +557,15 @@ def _backward_sig(g, key, make, x, outs_of, with_corr=False):
         g[f"{key}_pcorr"] = np.array(corr)
 
 
-def _frozen_bwd(g, key, make, seed, x, outs_of, nsamp=256):
-    """full-graph gradients with BatchNorm in evaluation mode (G12, G14): output samples, per-parameter gradient signature +
-    `nsamp` sampled elements, and the reference's own bf16-autocast deviation as calibration"""
+def _frozen_bwd(g, key, make, seed, x, outs_of, nsamp=256, xseed=None):
+    """full-graph gradients with BatchNorm in evaluation mode (G12, G14, G18): output samples, per-parameter gradient signature +
+    `nsamp` sampled elements, and the reference's own bf16-autocast deviation as calibration.  `xseed`: the caller drew
+    x = RandomState(xseed).rand(*x.shape); recorded so that a test rebuilds the input from the fixture alone.  Returns the
+    reference's bf16-autocast outputs (the callers that assert on them)."""
     import torch
+    if xseed is not None:
+        assert np.array_equal(x, np.random.RandomState(xseed).rand(*x.shape).astype(np.float32))
+        g[f"{key}_xseed"], g[f"{key}_xshape"] = np.array([xseed]), np.array(x.shape)
     m = make()
     fill_state_rs(m, seed)
     m.eval()
@@ -597,6 +605,7 @@ def _frozen_bwd(g, key, make, seed, x, outs_of, nsamp=256):
         gl = gr.detach().double().numpy().reshape(-1)
         cal.append([np.abs(gl[sidx[pi]] - sval[pi]).max() / (sig[pi][4] + 1e-30), abs(np.sqrt((gl ** 2).sum()) - sig[pi][2]) / (sig[pi][2] + 1e-30)])
     g[f"{key}_pcal"] = np.array(cal)
+    return [o.detach().numpy() for o in outs2]
 
 
 def gen_g11(ref_utils, ref_models):
@@ -809,6 +818,82 @@ def gen_g14(ref_models, ref_trainer):
     g["donms_status"] = np.array(status)                   # 0: None, 1: rows stored, -1: the reference raised IndexError
     np.savez_compressed(os.path.join(OUT, "g14_round5.npz"), **g)
     print("g14 written", os.path.getsize(os.path.join(OUT, "g14_round5.npz")) / 1e6, "MB; reference do_nms status", status)
+
+
+def _close_frac(got, ref, rel):
+    """fraction of the elements outside tests/test_gpu_model.py::_close's band, and the largest error over the largest element"""
+    got = np.asarray(got, np.float64).reshape(-1); ref = np.asarray(ref, np.float64).reshape(-1)
+    err = np.abs(got - ref)
+    return float((err > rel * np.abs(ref).max() + rel * np.abs(ref)).mean()), float(err.max() / (np.abs(ref).max() + 1e-30))
+
+
+G18_BN_PROBES = (("focus", 2e-2), ("backbone_stage2_conv", 2e-2), ("backbone_stage4_conv", 3e-2), ("head_stage4_bscp.cba3", 6e-2))
+
+
+def gen_g18(ref_models):
+    """G18: the whole network OFF THE SQUARE — H != W, a deepest map that is odd or smaller than the 5 x 5 pool window, batch 1 and
+    an odd batch — as G12 / G14 record it on squares: evaluation-mode BatchNorm under autograd (`_frozen_bwd`, 64 sampled
+    elements per parameter), and for the YOLOv5s keys one training-mode forward (sampled head outputs, running statistics of four
+    layers, as G11 does for m / l / x).  Asserts before writing that the reference's OWN bf16-autocast run stays inside the bars
+    the tests hold the HIP path to: a key that fails has the wrong shape or seed for this purpose.  Two files (size); sampled
+    values as float32, indices as int32."""
+    import torch
+    torch.set_num_threads(8)
+    v5 = lambda o: list(o)                                          # noqa: E731
+    cases = (  # key, file, model, batch, H, W, input seed, state seed, outs_of
+        ("v5s_96x160", "a", lambda: ref_models.YOLOV5Small(3, 80), 3, 96, 160, 1801, 1810, v5),
+        ("v5s_224x288", "a", lambda: ref_models.YOLOV5Small(3, 80), 1, 224, 288, 1802, 1820, v5),
+        ("v5s_416", "a", lambda: ref_models.YOLOV5Small(3, 80), 2, 416, 416, 1803, 1830, v5),
+        ("v5m_96x160", "b", lambda: ref_models.YOLOV5Middle(3, 80), 3, 96, 160, 1804, 1840, v5),
+        ("v5x_224x288", "b", lambda: ref_models.YOLOV5XLarge(3, 80), 1, 224, 288, 1805, 1850, v5),
+        ("yolox_96x160", "b", lambda: ref_models.YOLOXSmall(1, 3, 80, 0.01), 3, 96, 160, 1806, 1860, lambda o: list(o.values())),
+    )
+    files = {"a": {}, "b": {}}
+    for key, fl, make, B, H, W, xseed, seed, outs_of in cases:
+        g = files[fl]
+        x = np.random.RandomState(xseed).rand(B, 3, H, W).astype(np.float32)
+        outs_lo = _frozen_bwd(g, key, make, seed, x, outs_of, nsamp=64, xseed=xseed)
+        for i, lo in enumerate(outs_lo):                            # (1) the reference's bf16-autocast outputs on the stored samples
+            frac, worst = _close_frac(lo.reshape(-1)[g[f"{key}_out_idx{i}"]], g[f"{key}_out_val{i}"], 3e-2)
+            print(f"{key} out{i} {tuple(int(v) for v in g[f'{key}_out_shape{i}'])}: bf16 autocast vs fp32, worst error / largest element {worst:.4f}")
+            assert frac == 0.0, f"{key} out{i}: the reference's own bf16 run is outside 3e-2 ({frac:.4f} of the samples)"
+        cal = g[f"{key}_pcal"]
+        kinds = np.array([".bn." in str(n) for n in g[f"{key}_pnames"]])
+        print(f"{key}: {len(cal)} parameters; bf16-autocast calibration, worst element / norm deviation: weights "
+              f"{cal[~kinds, 0].max():.4f} / {cal[~kinds, 1].max():.4f}, BatchNorm affine {cal[kinds, 0].max():.4f} / {cal[kinds, 1].max():.4f}")
+        g[f"{key}_pidx"] = g[f"{key}_pidx"].astype(np.int32)
+        g[f"{key}_pval"] = g[f"{key}_pval"].astype(np.float32)
+        for i in range(len(outs_lo)):
+            g[f"{key}_out_idx{i}"] = g[f"{key}_out_idx{i}"].astype(np.int32)
+        if not key.startswith("v5s_"):
+            continue
+        # ---- one training-mode forward on the seeded default init (the constructor's dummy forward leaves running_mean 0, running_var
+        # 0.97 and one tracked batch: the running mean after this forward is all batch statistic, the count is 2)
+        torch.manual_seed(0)
+        m = make().train()
+        with torch.no_grad():
+            outs = m(torch.from_numpy(x.copy()))
+        torch.manual_seed(0)
+        m2 = make().train()
+        with torch.no_grad(), torch.autocast("cpu", dtype=torch.bfloat16):
+            m2(torch.from_numpy(x.copy()))
+        for i, o in enumerate(outs):
+            flat = o.numpy().reshape(-1)
+            idx = np.random.RandomState(seed + 20 + i).randint(0, flat.size, 2048)
+            g[f"{key}_train_shape{i}"] = np.array(o.shape)
+            g[f"{key}_train_idx{i}"], g[f"{key}_train_val{i}"] = idx.astype(np.int32), flat[idx]
+        mods, mods2 = dict(m.named_modules()), dict(m2.named_modules())
+        for pn, tol in G18_BN_PROBES:                               # (2) the reference's bf16-autocast running statistics
+            bn, bn2 = mods[pn].bn, mods2[pn].bn
+            g[f"{key}_rm_{pn}"], g[f"{key}_rv_{pn}"] = bn.running_mean.numpy().copy(), bn.running_var.numpy().copy()
+            g[f"{key}_nbt_{pn}"] = np.array([int(bn.num_batches_tracked)])
+            for what, a, b in (("running_mean", bn2.running_mean, bn.running_mean), ("running_var", bn2.running_var, bn.running_var)):
+                frac, worst = _close_frac(a.numpy(), b.numpy(), tol)
+                print(f"{key} {pn} {what}: bf16 autocast vs fp32, worst error / largest element {worst:.4f}, outside {tol:g}: {frac:.4f}")
+                assert frac <= 0.01, f"{key} {pn} {what}: the reference's own bf16 run is outside {tol:g} on {frac:.4f} of the channels"
+    for fl, name in (("a", "g18_shapes.npz"), ("b", "g18_shapes_b.npz")):
+        np.savez_compressed(os.path.join(OUT, name), **files[fl])
+        print(name, "written", os.path.getsize(os.path.join(OUT, name)) / 1e6, "MB")
 
 
 def _g15_boxes(seed, B, img, nc, maxb, minb=1, lo=8.0, hi=None, empty=(), extra=None):
