@@ -131,16 +131,19 @@ typedef struct yh_conv_desc {
     const float* bnr_ws;
     float*   bnr_part;
 } yh_conv_desc;
-/* number of partial-sum rows the conv kernel writes for this shape */
+/* number of partial-sum rows the conv kernel writes for this shape: those of the launch yh_conv_igemm makes for the same
+ * descriptor (an algo that is not eligible answers as algo 0 does, which is what then runs) */
 int yh_conv_stat_blocks(const yh_conv_desc* d);
 int yh_conv_igemm(const yh_conv_desc* d, yh_stream stream);
 /* name of the kernel instantiation yh_conv_igemm launches for this descriptor ("conv_v2_kernel<128, 2, 2, 2, 1>"),
  * as rocprofv3 prints it: lets bench.py report per-kernel numbers that line up with the profiler's */
 int yh_conv_kernel_name(const yh_conv_desc* d, char* buf, int buflen);
-/* rows of the bnr_part slab for this data-gradient descriptor; 0 = fused reduction not available for it */
+/* rows of the bnr_part slab for this data-gradient descriptor, as the launch yh_conv_igemm makes for the same descriptor writes
+ * them; 0 = fused reduction not available for it */
 int yh_conv_bnr_rows(const yh_conv_desc* d);
 /* What yh_conv_igemm(d) will launch — family, rows of both slabs, instantiation — decided by the same plan: the three queries
- * above in one call.  Needs no device and dereferences no operand.  Returns the rc yh_conv_igemm would return from its own argument
+ * above in one call, so the rows are those of the launch yh_conv_igemm makes for the same descriptor (where its algo is not
+ * eligible: every field as with algo 0).  Needs no device and dereferences no operand.  Returns the rc yh_conv_igemm would return from its own argument
  * checks; `out` is filled from the dims alone whenever they are positive (as yh_conv_stat_blocks answers), also beside a non-zero
  * rc such as a null operand. */
 enum { YH_CONV_FAM_GENERIC = 0, YH_CONV_FAM_V2, YH_CONV_FAM_V3, YH_CONV_FAM_HALO, YH_CONV_FAM_HALO160, YH_CONV_FAM_STEM,

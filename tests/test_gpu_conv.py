@@ -1037,6 +1037,79 @@ def _dgrad_check(dev, B, H, W, Cin, Cout, k, s, p, algo, tile_k=0, tile_n=0):
     assert torch.allclose(got[1], (dz * zz).sum(0), rtol=2e-3, atol=2e-3 * (dz * zz).abs().sum(0).max().item())
 
 
+def _info(d):
+    import ctypes as C
+    from yoloseries_amd._lib import ConvInfo, lib
+    o = ConvInfo()
+    rc = lib().yh_conv_info(C.byref(d), C.byref(o))
+    return (rc,) + tuple(getattr(o, n) for n, _ in ConvInfo._fields_)
+
+
+_DECLINED = {}         # mode -> (operands, launch(algo) -> (rows, output, slab)), the algo-0 result among them: made once
+
+
+def _declined_case(dev, mode):
+    """ConvBnAct(128, 128, 3, 1, 1) on 32 x 40 x 40: the smallest batch at this map at which the default plan (the halo kernel: 32 * 7
+    patches >= 128) and the plan of the same descriptor under a sibling's algo number (no halo kernel; 32 * 1600 >= 49 152 pixels: the
+    256 x 128 ring tile, 200 rows) differ with the default the larger (224 rows).  mode "fwd": forward with statistics; "dgrad": data
+    gradient with the fused BatchNorm-backward reduction, set up as _dgrad_check does"""
+    if mode in _DECLINED:
+        return _DECLINED[mode]
+    import ctypes as C
+    from yoloseries_amd import hipk
+    from yoloseries_amd._lib import lib
+    B, H, W, Ch = 32, 40, 40, 128
+    src = _nhwc(B, H, W, Ch, dev, 91)
+    g = torch.Generator().manual_seed(92)
+    w = (torch.randn(Ch, Ch, 3, 3, generator=g) / (9 * Ch) ** 0.5).to(torch.bfloat16).float().to(dev)
+    z = _nhwc(B, H, W, Ch, dev, 93)
+    ws = torch.cat([torch.rand(Ch, generator=g) + 0.5, torch.randn(Ch, generator=g)]).to(dev)
+    wp = hipk.pack_weight_fwd(w) if mode == "fwd" else hipk.pack_weight_dgrad(w)
+    dummy = torch.zeros(4, device=dev)
+    keep = (src, w, z, ws, wp, dummy)
+
+    def launch(algo):
+        out = torch.full((B, H, W, Ch), 3.0, dtype=torch.bfloat16, device=dev)
+        d = hipk.conv_desc([hipk.full(src)], hipk.YH_CONV_FWD if mode == "fwd" else hipk.YH_CONV_DGRAD, B, H, W, H, W, 3, 1, 1, wp, Ch, hipk.full(out))
+        d.algo = algo
+        if mode == "fwd":
+            d.stats = dummy.data_ptr()
+            rows = hipk.conv_stat_blocks(d)
+        else:
+            rows = lib().yh_conv_bnr_rows(C.byref(d))
+            d.bnr_z, d.bnr_ldz, d.bnr_C, d.bnr_ws, d.bnr_part = z.data_ptr(), Ch, Ch, ws.data_ptr(), dummy.data_ptr()
+            assert lib().yh_conv_bnr_rows(C.byref(d)) == rows
+        assert rows > 0
+        slab = torch.full((rows + 64, 2, wp.shape[0] if mode == "fwd" else Ch), float("nan"), device=dev)       # 64 guard rows
+        if mode == "fwd":
+            d.stats = slab.data_ptr()
+        else:
+            d.bnr_part = slab.data_ptr()
+        info = _info(d)
+        hipk.conv_launch(d)
+        torch.cuda.synchronize()
+        return rows, info, out, slab
+
+    _DECLINED[mode] = keep, launch, launch(0)
+    return _DECLINED[mode]
+
+
+@pytest.mark.parametrize("mode,algo", [("fwd", 7), ("fwd", 9), ("fwd", 13), ("dgrad", 9)])
+def test_conv_declined_sibling_rows_are_those_of_the_launch(dev, mode, algo):
+    """A descriptor whose algo names a sibling family that does not take it runs the library default: the rows the queries report
+    are those this launch writes — a slab of exactly that many rows is filled, the guard rows behind it stay untouched — and the query,
+    the output and the slab are those of the same descriptor with algo 0, bit for bit (same kernel, same grid, fixed-order sums)"""
+    _, launch, (rows0, info0, out0, slab0) = _declined_case(dev, mode)
+    rows, info, out, slab = launch(algo)
+    print(f"{mode} algo {algo}: rows {rows} (algo 0: {rows0}), {info[-1].decode()}; rows written: {int(torch.isfinite(slab).all(2).all(1).sum())}")
+    assert info[0] == 0 and b"conv_halo_kernel<128" in info[-1], info
+    assert torch.isfinite(slab[:rows]).all() and torch.isnan(slab[rows:]).all()
+    assert torch.isfinite(slab0[:rows0]).all() and torch.isnan(slab0[rows0:]).all()
+    assert rows == rows0 and info == info0
+    assert rows == info[4 if mode == "fwd" else 5]          # yh_conv_plan_info.stat_rows / .bnr_rows
+    assert torch.equal(out, out0) and torch.equal(slab.view(torch.int32), slab0.view(torch.int32))
+
+
 @pytest.mark.parametrize("algo", [1, 2, 3, 4])
 def test_conv_concat_upsample_algos(dev, algo):
     """two-segment input, the first read through the nearest-2x upsample, folded BN + SiLU, residual, split destination"""

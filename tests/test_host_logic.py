@@ -354,8 +354,8 @@ def test_conv_plan_table_is_stable():
     """what yh_conv_igemm decides — kernel instantiation, BatchNorm partial-sum rows, fused-reduction rows — for every shipped entry of
     the tuning table and 2 000 seeded random descriptors (invalid ones and their return codes included), through the C ABI alone,
     against the record tests/golden/conv_plan_digest.json: one sha256 per 100 lines of the table and the set of kernel
-    instantiations (`tools/conv_plan_table.py --digest`, taken from the library as it was before the planner was consolidated
-    into conv_plan).  Planning is host code: no device needed.  A deliberate change of a plan — a new family, another tile —
+    instantiations (`tools/conv_plan_table.py --digest`; lines and names as before the planner was consolidated into conv_plan, the
+    rows of declined sibling requests — six chunks — as they are since those answer like algo 0).  Planning is host code: no device needed.  A deliberate change of a plan — a new family, another tile —
     regenerates the record; `tools/conv_plan_table.py --reduced` prints the lines of a chunk that differs"""
     import json
     from yoloseries_amd._lib import lib
@@ -416,6 +416,42 @@ def test_conv_info_agrees_with_the_three_queries():
         assert L.yh_conv_info(C.byref(d), C.byref(o)) == 0 and L.yh_conv_info(C.byref(bare), C.byref(ob)) != 0
         assert (o.family, o.variant, o.tail, o.name) == want and o.stat_rows > 0
         assert all(getattr(o, n) == getattr(ob, n) for n, _ in _lib.ConvInfo._fields_)
+
+
+def test_declined_sibling_request_answers_as_algo_0():
+    """A descriptor whose algo names a sibling family (7 .. 13) that does not take it — 11, unassigned, never does — runs the plan of
+    the same descriptor with algo 0, so every query answers as that one: all fields of yh_conv_info and its rc, yh_conv_stat_blocks
+    and yh_conv_bnr_rows.  Over the reduced corpus of tools/conv_plan_table.py (530 shipped entries, 2 000 seeded random descriptors)
+    x the seven algos; the counts are a property of tune_defaults.json and the seed"""
+    import ctypes as C
+    import random
+    from yoloseries_amd import _lib
+    mod, L = _conv_plan_table(), _lib.lib()
+    cases = [mod.case_of_key(f) for _, f, _ in mod.table_keys()]
+    r = random.Random(20261016)
+    cases += [mod.random_case(r) for _ in range(2000)]
+
+    def ask(c, algo):
+        d, o = mod.make_desc(dict(c, algo=algo)), _lib.ConvInfo()
+        rc = L.yh_conv_info(C.byref(d), C.byref(o))
+        return (rc,) + tuple(getattr(o, n) for n, _ in _lib.ConvInfo._fields_), (L.yh_conv_stat_blocks(C.byref(d)), L.yh_conv_bnr_rows(C.byref(d)))
+
+    fields = [n for n, _ in _lib.ConvInfo._fields_]
+    i_fam, i_stat, i_bnr = (1 + fields.index(n) for n in ("family", "stat_rows", "bnr_rows"))
+    declined, honoured, bad = 0, 0, []
+    for c in cases:
+        info0, rows0 = ask(c, 0)
+        for algo in (7, 8, 9, 10, 11, 12, 13):
+            info, rows = ask(c, algo)
+            assert rows == (info[i_stat], info[i_bnr]), (c, algo)
+            if algo != 11 and info[i_fam] == _lib.CONV_ALGO_FAMILY[algo][0]:
+                honoured += 1
+                continue
+            declined += 1
+            if (info, rows) != (info0, rows0):
+                bad.append((algo, c, info, info0))
+    assert (declined, honoured) == (17371, 339), (declined, honoured)
+    assert not bad, (len(bad), bad[:3])
 
 
 CONV_PREFIX_GROUPS = {("conv6", "conv11", "dgrad"): 50, ("conv6", "conv11", "fwd"): 24, ("conv9", "conv11", "eval"): 6, ("conv9", "conv10", "eval"): 2}

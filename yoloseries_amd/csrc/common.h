@@ -108,27 +108,41 @@ inline void yh_lds_limit(YhDevOnce& once, std::initializer_list<YhLdsLimit> limi
 #define YH_CHECK_LAUNCH(name) do { hipError_t e_ = hipGetLastError(); \
     if (e_ != hipSuccess) { yh_set_error("%s: launch failed: %s", name, hipGetErrorString(e_)); return YH_ELAUNCH; } } while (0)
 
-// conv_dg2.hip: the stride-2 data-gradient kernel behind yh_conv_igemm (algo 7)
-int yh_dg2_rows(const yh_conv_desc* d);                 // grid rows (== slab rows of the fused reduction); 0 = not eligible
-int yh_dg2_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len);
+static inline bool yh_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-// conv_p3.hip: the 3x3 / stride-1 patch kernel for small channel counts behind yh_conv_igemm (algo 8)
-int yh_p3_rows(const yh_conv_desc* d);                  // grid rows (== statistics / fused-reduction slab rows); 0 = not eligible
-int yh_p3_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len);
+// an epilogue of a conv beyond the plain store: affine / activation / residual / second destination (_na: accumulation aside)
+inline bool conv_generic_na(const yh_conv_desc* d) { return d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->nsplit < d->N; }
+inline bool conv_generic(const yh_conv_desc* d) { return conv_generic_na(d) || d->accumulate; }
+// the operands of the fused BatchNorm-backward reduction (d->bnr_part) as every kernel with that epilogue reads them
+inline bool conv_bnr_operands(const yh_conv_desc* d) { return d->bnr_z && yh_aligned16(d->bnr_z) && d->bnr_ldz % 8 == 0 && d->bnr_ws && d->bnr_C >= d->N; }
 
-// conv_h80.hip: the 80-channel 3x3 halo kernel (YOLOv5x stage 1, inference epilogues) behind yh_conv_igemm (algo 9)
-int yh_h80_rows(const yh_conv_desc* d);                 // grid rows; 0 = not eligible
-int yh_h80_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len);
-
-// conv_pw.hip: the pointwise (1x1) kernel for the 80- / 160-channel layers of YOLOv5x (inference epilogues) behind yh_conv_igemm (algo 10)
-int yh_c80_rows(const yh_conv_desc* d);                 // grid size; 0 = not eligible (conv_c80.hip)
-int yh_c80_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len);
-int yh_pw_rows(const yh_conv_desc* d);                  // grid rows; 0 = not eligible
-int yh_pw_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len);
-
-// conv_pt.hip: the pointwise (1x1) kernel of the TRAINING step (128 / 256 input channels; all four epilogues) behind yh_conv_igemm (algo 13)
-int yh_pt_rows(const yh_conv_desc* d);                  // pixel slots of the grid (== statistics / fused-reduction slab rows); 0 = not eligible
-int yh_pt_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len);
+// ---- the sibling kernel families behind yh_conv_igemm (d->algo), two functions each, both made from ONE <s>_plan(d) of their file:
+//   yh_<s>_info:   what the plan says, without a stream: out->rows = its grid rows along x (the rows of the slabs the family writes)
+//                  and out->name = the instantiation as profilers print it; returns the rc of the operand checks that stand before
+//                  the launch (the name stays empty where they fail)
+//   yh_<s>_launch: plans, checks, launches
+// Either answers YH_CONV_DECLINED (info: with rows 0) and sets no error text where the plan does not take the descriptor: the
+// dispatcher (conv_choose in conv_igemm.hip) then goes on with the library default.
+constexpr int YH_CONV_DECLINED = 1;
+struct ConvSibInfo { int rows; char name[96]; };
+// conv_dg2.hip: the stride-2 data-gradient kernel (algo 7)
+int yh_dg2_info(const yh_conv_desc* d, ConvSibInfo* out);
+int yh_dg2_launch(const yh_conv_desc* d, yh_stream stream);
+// conv_p3.hip: the 3x3 / stride-1 patch kernel for small channel counts (algo 8)
+int yh_p3_info(const yh_conv_desc* d, ConvSibInfo* out);
+int yh_p3_launch(const yh_conv_desc* d, yh_stream stream);
+// conv_h80.hip: the 80-channel 3x3 halo kernel (YOLOv5x stage 1, inference epilogues; algo 9)
+int yh_h80_info(const yh_conv_desc* d, ConvSibInfo* out);
+int yh_h80_launch(const yh_conv_desc* d, yh_stream stream);
+// conv_pw.hip: the pointwise (1x1) kernel for the 80- / 160- / 320-channel layers of YOLOv5x (inference epilogues; algo 10)
+int yh_pw_info(const yh_conv_desc* d, ConvSibInfo* out);
+int yh_pw_launch(const yh_conv_desc* d, yh_stream stream);
+// conv_c80.hip: the 80 -> 160 channel tap kernel (inference epilogue; algo 12)
+int yh_c80_info(const yh_conv_desc* d, ConvSibInfo* out);
+int yh_c80_launch(const yh_conv_desc* d, yh_stream stream);
+// conv_pt.hip: the pointwise (1x1) kernel of the TRAINING step (all four epilogues; algo 13; rows = pixel slots of its grid)
+int yh_pt_info(const yh_conv_desc* d, ConvSibInfo* out);
+int yh_pt_launch(const yh_conv_desc* d, yh_stream stream);
 
 // conv_wgp.hip: the patch form of the weight gradient behind yh_conv_wgrad (tile_k 40)
 int yh_wgp_ok(const yh_wgrad_desc* d);
@@ -140,5 +154,3 @@ int yh_wgs_tiles(const yh_wgrad_desc* d);
 const char* yh_wgs_name(const yh_wgrad_desc* d);
 size_t yh_wgs_ws_bytes(const yh_wgrad_desc* d);
 int yh_wgs_run(const yh_wgrad_desc* d, yh_stream stream);
-
-static inline bool yh_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }

@@ -308,17 +308,19 @@ bool c80_plan(const yh_conv_desc* d, C80Plan* pl)
 /* diagnostics: a device buffer of grid x 4 x 16 uint64 that receives shader-clock stamps of every wave's third tile (NULL: off) */
 extern "C" void yh_c80_set_stamps(void* p) { g_c80_stamps = (unsigned long long*)p; }
 
-int yh_c80_rows(const yh_conv_desc* d)
+// entry points used by conv_igemm.hip (yh_conv_igemm with algo 12; common.h): rows and kernel name of the plan / its launch
+int yh_c80_info(const yh_conv_desc* d, ConvSibInfo* out)
 {
     C80Plan pl;
-    return c80_plan(d, &pl) ? pl.grid : 0;
+    if (!(out->rows = c80_plan(d, &pl) ? pl.grid : 0)) return YH_CONV_DECLINED;
+    snprintf(out->name, sizeof(out->name), "conv_c80_kernel");
+    return YH_OK;
 }
 
-int yh_c80_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len)
+int yh_c80_launch(const yh_conv_desc* d, yh_stream stream)
 {
     C80Plan pl;
-    YH_CHECK_ARG(c80_plan(d, &pl), "yh_conv_igemm: algo 12 (80 -> 160 channel tap kernel) is not eligible for this descriptor");
-    if (name_out) { snprintf(name_out, name_len, "conv_c80_kernel"); return YH_OK; }
+    if (!c80_plan(d, &pl)) return YH_CONV_DECLINED;
     static YhDevOnce attr_set;
     yh_lds_limit(attr_set, {{(const void*)conv_c80_kernel, C80_SMEM}});
     conv_c80_kernel<<<dim3(pl.grid), dim3(256), C80_SMEM, (hipStream_t)stream>>>(pl.k);

@@ -380,21 +380,22 @@ bool dg2_plan(const yh_conv_desc* d, Dg2Plan* pl)
 
 }  // namespace
 
-// entry points used by conv_igemm.hip (yh_conv_igemm with algo 7): eligibility + grid rows, kernel name, launch
-int yh_dg2_rows(const yh_conv_desc* d)
+// entry points used by conv_igemm.hip (yh_conv_igemm with algo 7; common.h): rows and kernel name of the plan / its launch
+int yh_dg2_info(const yh_conv_desc* d, ConvSibInfo* out)
 {
     Dg2Plan pl;
-    return dg2_plan(d, &pl) ? pl.gx : 0;
+    if (!(out->rows = dg2_plan(d, &pl) ? pl.gx : 0)) return YH_CONV_DECLINED;
+    YH_CHECK_ARG(!d->bnr_part || conv_bnr_operands(d), "yh_conv_igemm: bad fused-reduction operands");
+    snprintf(out->name, sizeof(out->name), "conv_dg2_kernel<%d, %d, %d, %d>", pl.ct, pl.kc, d->bnr_part ? 3 : 0, pl.pt);
+    return YH_OK;
 }
 
-int yh_dg2_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len)
+int yh_dg2_launch(const yh_conv_desc* d, yh_stream stream)
 {
     Dg2Plan pl;
-    YH_CHECK_ARG(dg2_plan(d, &pl), "yh_conv_igemm: algo 7 (stride-2 data-gradient kernel) is not eligible for this descriptor");
+    if (!dg2_plan(d, &pl)) return YH_CONV_DECLINED;
+    YH_CHECK_ARG(!d->bnr_part || conv_bnr_operands(d), "yh_conv_igemm: bad fused-reduction operands");
     const int epi = d->bnr_part ? 3 : 0;
-    if (d->bnr_part)
-        YH_CHECK_ARG(d->bnr_z && yh_aligned16(d->bnr_z) && d->bnr_ldz % 8 == 0 && d->bnr_ws && d->bnr_C >= d->N, "yh_conv_igemm: bad fused-reduction operands");
-    if (name_out) { snprintf(name_out, name_len, "conv_dg2_kernel<%d, %d, %d, %d>", pl.ct, pl.kc, epi, pl.pt); return YH_OK; }
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(pl.gx, pl.gy), blk(256 * pl.ct);
 #define YH_LAUNCH_DG2(CT_, KC_, PT_)                                                                                   \

@@ -409,8 +409,7 @@ bool h80_plan(const yh_conv_desc* d, H80Plan* pl)
     k.imgbytes = (unsigned)ib; k.wbytes = (unsigned)wb;
     static const int dbg = getenv("YH_H80_DBG") ? atoi(getenv("YH_H80_DBG")) : 0;
     k.dbg = dbg;
-    const bool generic = d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->accumulate || d->nsplit < d->N;
-    pl->epi = generic ? 2 : 0;
+    pl->epi = conv_generic(d) ? 2 : 0;
     pl->gy = d->N / 80;
     int cap = 256 / pl->gy;
     if (cap < 1) cap = 1;
@@ -421,17 +420,19 @@ bool h80_plan(const yh_conv_desc* d, H80Plan* pl)
 
 }  // namespace
 
-int yh_h80_rows(const yh_conv_desc* d)
+// entry points used by conv_igemm.hip (yh_conv_igemm with algo 9; common.h): rows and kernel name of the plan / its launch
+int yh_h80_info(const yh_conv_desc* d, ConvSibInfo* out)
 {
     H80Plan pl;
-    return h80_plan(d, &pl) ? pl.gx : 0;
+    if (!(out->rows = h80_plan(d, &pl) ? pl.gx : 0)) return YH_CONV_DECLINED;
+    snprintf(out->name, sizeof(out->name), "conv_h80_kernel<80, 5, %d>", pl.epi);
+    return YH_OK;
 }
 
-int yh_h80_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len)
+int yh_h80_launch(const yh_conv_desc* d, yh_stream stream)
 {
     H80Plan pl;
-    YH_CHECK_ARG(h80_plan(d, &pl), "yh_conv_igemm: algo 9 (80-channel halo kernel) is not eligible for this descriptor");
-    if (name_out) { snprintf(name_out, name_len, "conv_h80_kernel<80, 5, %d>", pl.epi); return YH_OK; }
+    if (!h80_plan(d, &pl)) return YH_CONV_DECLINED;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(pl.gx, pl.gy), blk(512);
     constexpr int sm = H80Cfg<80, 5>::SMEM;

@@ -10,7 +10,9 @@
 //
 // This file is host code only: it plans a launch (conv_plan: family, instantiation, grid, slab rows) and answers the queries from
 // the same plan.  The kernels and the template dispatch of each family are in conv_generic.hip, conv_v2.hip, conv_v3.hip,
-// conv_halo.hip, conv_halo160.hip and conv_stem.hip; conv_igemm.h is what they share with this file.
+// conv_halo.hip, conv_halo160.hip and conv_stem.hip; conv_igemm.h is what they share with this file.  The sibling families behind
+// d->algo 7..13 plan in their own files (common.h); conv_choose decides once per call between them and the chain, for the launcher
+// and every query alike.
 #include "conv_igemm.h"
 #include <stdlib.h>
 
@@ -72,10 +74,7 @@ int conv_halo_map() {
     return v;
 }
 
-// an epilogue beyond the plain store: affine / activation / residual / second destination (_na: accumulation aside)
-inline bool conv_generic_na(const yh_conv_desc* d) { return d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->nsplit < d->N; }
-inline bool conv_generic(const yh_conv_desc* d) { return conv_generic_na(d) || d->accumulate; }
-// epilogue of the v2 / v3 / halo kernels: 3 fused BatchNorm-backward reduction, 2 generic, 1 BatchNorm partial sums, 0 plain store
+// epilogue of the v2 / v3 / halo kernels: 3 fused BatchNorm-backward reduction, 2 generic (conv_generic, common.h), 1 BatchNorm partial sums, 0 plain store
 inline int conv_epi(const yh_conv_desc* d) { return d->bnr_part ? 3 : (conv_generic(d) ? 2 : (d->stats ? 1 : 0)); }
 // stride-2 data gradient processed as four parity classes of output pixels (cls_slot)
 inline bool conv_cls(const yh_conv_desc* d) {
@@ -403,47 +402,37 @@ int conv_launch(const ConvPlan& pl, hipStream_t st)
 
 // ---- sibling families (own files, each with its own *_plan) behind d->algo: stride-2 data-gradient kernel (conv_dg2.hip), 3x3 patch
 // kernel (conv_p3.hip), 80-channel halo kernel (conv_h80.hip), pointwise kernels (conv_pw.hip, conv_pt.hip), 80 -> 160 kernel
-// (conv_c80.hip).  `who`: the entry points that hand the algo over (11 is unassigned: the launcher runs the default for it)
-enum { SIB_RUN = 1, SIB_STAT = 2, SIB_BNR = 4 };
-struct ConvSibling { int algo, who, family; int (*rows)(const yh_conv_desc*); int (*run)(const yh_conv_desc*, yh_stream, char*, int); };
+// (conv_c80.hip); 11 is unassigned and so always declines.  `slabs`: the partial-sum slabs the family's kernels write, which are as many
+// rows as its grid; a slab it does not write has the rows the chain plans for the descriptor (no launch of the family writes them)
+enum ConvSlabs { SLABS_NONE, SLABS_BNR, SLABS_BOTH };          // none / fused reduction / statistics and fused reduction
+struct ConvSibling { int algo, family; ConvSlabs slabs; int (*info)(const yh_conv_desc*, ConvSibInfo*); int (*launch)(const yh_conv_desc*, yh_stream); };
 const ConvSibling CONV_SIBLINGS[] = {
-    {7, SIB_RUN | SIB_BNR, YH_CONV_FAM_DG2, yh_dg2_rows, yh_dg2_run},   {8, SIB_RUN | SIB_STAT | SIB_BNR, YH_CONV_FAM_P3, yh_p3_rows, yh_p3_run},
-    {9, SIB_RUN, YH_CONV_FAM_H80, yh_h80_rows, yh_h80_run},             {10, SIB_RUN, YH_CONV_FAM_PW, yh_pw_rows, yh_pw_run},
-    {11, SIB_RUN, 0, nullptr, nullptr},                                 {12, SIB_RUN, YH_CONV_FAM_C80, yh_c80_rows, yh_c80_run},
-    {13, SIB_RUN | SIB_STAT | SIB_BNR, YH_CONV_FAM_PT, yh_pt_rows, yh_pt_run},
+    {7, YH_CONV_FAM_DG2, SLABS_BNR, yh_dg2_info, yh_dg2_launch},    {8, YH_CONV_FAM_P3, SLABS_BOTH, yh_p3_info, yh_p3_launch},
+    {9, YH_CONV_FAM_H80, SLABS_NONE, yh_h80_info, yh_h80_launch},   {10, YH_CONV_FAM_PW, SLABS_NONE, yh_pw_info, yh_pw_launch},
+    {11, 0, SLABS_NONE, nullptr, nullptr},                          {12, YH_CONV_FAM_C80, SLABS_NONE, yh_c80_info, yh_c80_launch},
+    {13, YH_CONV_FAM_PT, SLABS_BOTH, yh_pt_info, yh_pt_launch},
 };
-// the sibling that takes the descriptor for entry point `who` (*rows: its grid rows), or nullptr.  Where the sibling of d->algo
-// declines, the library default (algo 0) plans instead: d then points to such a copy in *d0 — except for yh_conv_stat_blocks, which
-// has always gone on with the algo as it stands
-const ConvSibling* conv_sibling(const yh_conv_desc*& d, yh_conv_desc* d0, int who, int* rows)
+
+// The one choice behind the launcher and all four queries, made once per call for a plannable d:
+//   - the sibling row of d->algo takes d: `sib` (`rc`: its answer), and the chain does not plan;
+//   - the row declines, or is unassigned: the chain plans (`pl`) the algo-0 copy of d in `d0`;
+//   - there is no such row: the chain plans d as it stands.
+// `ask(row)`: how the caller puts d to the sibling, which plans once either way: the launcher by its launch (which, where the
+// sibling takes d, is the launch), yh_conv_info by its info.  One sibling plan and one chain plan at the most.
+struct ConvChoice { const ConvSibling* sib; int rc; const yh_conv_desc* d; yh_conv_desc d0; ConvPlan pl; };
+template <class Ask> void conv_choose(const yh_conv_desc* d, ConvChoice* c, Ask ask)
 {
+    c->sib = nullptr; c->d = d;
     for (const ConvSibling& s : CONV_SIBLINGS)
-        if (s.algo == d->algo && (s.who & who)) {
-            if (s.rows && (*rows = s.rows(d)) > 0) return &s;
-            if (who != SIB_STAT) { *d0 = *d; d0->algo = 0; d = d0; }
+        if (s.algo == d->algo) {
+            c->rc = s.info ? ask(s) : YH_CONV_DECLINED;
+            if (c->rc != YH_CONV_DECLINED) { c->sib = &s; return; }
+            c->d0 = *d; c->d0.algo = 0; c->d = &c->d0;
             break;
         }
-    return nullptr;
+    conv_plan(c->d, &c->pl);
 }
-
-// what entry point `who` (SIB_*) is answered from: the sibling that takes d (`rows`: its grid rows), else the plan `pl` of `d`,
-// which then is the caller's descriptor or the algo-0 copy of it in `d0` (conv_sibling).  The one path behind the launcher and
-// all four queries.  d must be plannable.
-struct ConvChoice { const ConvSibling* sib; int rows; const yh_conv_desc* d; yh_conv_desc d0; ConvPlan pl; };
-void conv_choose(const yh_conv_desc* d, int who, ConvChoice* c)
-{
-    c->d = d;
-    c->sib = conv_sibling(c->d, &c->d0, who, &c->rows);
-    if (!c->sib) conv_plan(c->d, &c->pl);
-}
-// rows of the statistics slab (SIB_STAT) / of the fused-reduction slab (SIB_BNR)
-int conv_rows(const yh_conv_desc* d, int who)
-{
-    ConvChoice c;
-    conv_choose(d, who, &c);
-    return c.sib ? c.rows : (who == SIB_STAT ? c.pl.stat_rows : c.pl.bnr_rows);
-}
-// yh_conv_bnr_rows' own preconditions, asked before it plans
+// yh_conv_bnr_rows' own preconditions, which need no plan
 bool conv_bnr_possible(const yh_conv_desc* d)
 {
     if (d->mode != YH_CONV_DGRAD || d->nseg != 1 || d->seg[0].C % 8 || d->seg[0].ups || d->N % 8) return false;
@@ -489,8 +478,7 @@ int conv_check_plan(const yh_conv_desc* d, const ConvPlan& pl)
     if (d->bnr_part && pl.family != FAM_STEM) {
         YH_CHECK_ARG((pl.k.v2 || pl.family == FAM_V3) && !conv_generic_na(d) && !d->stats && d->mode == YH_CONV_DGRAD,
                      "yh_conv_igemm: the fused BatchNorm-backward reduction needs the plain buffer-load data-gradient path");
-        YH_CHECK_ARG(d->bnr_z && yh_aligned16(d->bnr_z) && d->bnr_ldz % 8 == 0 && d->bnr_ws && d->bnr_C >= d->N && d->N % 8 == 0,
-                     "yh_conv_igemm: bad fused-reduction operands");
+        YH_CHECK_ARG(conv_bnr_operands(d) && d->N % 8 == 0, "yh_conv_igemm: bad fused-reduction operands");
     }
     if (pl.family == FAM_HALO160 || pl.family == FAM_HALO) YH_CHECK_ARG(pl.k.v2 && !pl.k.cls, "yh_conv_igemm: the halo kernel needs the buffer-load path");
     return YH_OK;
@@ -506,15 +494,15 @@ extern "C" int yh_conv_igemm(const yh_conv_desc* d, yh_stream stream)
 {
     if (const int rc = conv_check_args(d)) return rc;
     ConvChoice c;
-    conv_choose(d, SIB_RUN, &c);
-    if (c.sib) return c.sib->run(c.d, stream, nullptr, 0);
+    conv_choose(d, &c, [&](const ConvSibling& s) { return s.launch(d, stream); });
+    if (c.sib) return c.rc;
     if (const int rc = conv_check_plan(c.d, c.pl)) return rc;
     return conv_launch(c.pl, (hipStream_t)stream);
 }
 
 /* what yh_conv_igemm(d) will launch (include/yolohip.h): the rc of the launch's checks; `out` is filled from the dims alone
- * whenever the descriptor is plannable.  (A sibling's name comes from its launcher, which checks its fused-reduction operands
- * first: without them the name stays empty.) */
+ * whenever the descriptor is plannable.  (A sibling checks its fused-reduction operands before it names its kernel: without them
+ * the name stays empty.) */
 extern "C" int yh_conv_info(const yh_conv_desc* d, yh_conv_plan_info* out)
 {
     YH_CHECK_ARG(out != nullptr, "yh_conv_info: null out");
@@ -522,11 +510,13 @@ extern "C" int yh_conv_info(const yh_conv_desc* d, yh_conv_plan_info* out)
     int rc = conv_check_args(d);
     if (!conv_desc_plannable(d)) return rc;
     ConvChoice c;
-    conv_choose(d, SIB_RUN, &c);
+    ConvSibInfo si = {};
+    conv_choose(d, &c, [&](const ConvSibling& s) { return s.info(d, &si); });
     if (c.sib) {
         out->family = c.sib->family;
-        const int rc_name = c.sib->run(c.d, nullptr, out->name, (int)sizeof(out->name));
-        if (rc == YH_OK) rc = rc_name;
+        snprintf(out->name, sizeof(out->name), "%s", si.name);
+        if (rc == YH_OK) rc = c.rc;
+        if (c.sib->slabs != SLABS_BOTH) conv_plan(d, &c.pl);          // a slab the family does not write: the chain's rows for d as it stands
     } else {
         out->family = conv_public_family(c.pl.family);
         out->variant = c.pl.v3;
@@ -534,8 +524,9 @@ extern "C" int yh_conv_info(const yh_conv_desc* d, yh_conv_plan_info* out)
         conv_plan_name(c.pl, out->name, (int)sizeof(out->name));
         if (rc == YH_OK) rc = conv_check_plan(c.d, c.pl);
     }
-    out->stat_rows = conv_rows(d, SIB_STAT);
-    out->bnr_rows = conv_bnr_possible(d) ? conv_rows(d, SIB_BNR) : 0;
+    // the slabs: the sibling's grid rows where its family writes that slab, else what the chain planned
+    out->stat_rows = c.sib && c.sib->slabs == SLABS_BOTH ? si.rows : c.pl.stat_rows;
+    if (conv_bnr_possible(d)) out->bnr_rows = c.sib && c.sib->slabs != SLABS_NONE ? si.rows : c.pl.bnr_rows;
     return rc;
 }
 
@@ -549,16 +540,13 @@ extern "C" int yh_conv_kernel_name(const yh_conv_desc* d, char* buf, int buflen)
     return rc;
 }
 
-/* rows of the BatchNorm partial-sum slab (d->stats) the launch for this descriptor writes */
-extern "C" int yh_conv_stat_blocks(const yh_conv_desc* d) { return conv_desc_plannable(d) ? conv_rows(d, SIB_STAT) : 0; }
+/* rows of the BatchNorm partial-sum slab (d->stats) the launch for this descriptor writes (0 while the descriptor is not plannable) */
+extern "C" int yh_conv_stat_blocks(const yh_conv_desc* d) { yh_conv_plan_info o = {}; yh_conv_info(d, &o); return o.stat_rows; }
 
 /* rows of the partial-sum slab a data-gradient launch with the fused BatchNorm-backward reduction (bnr_*) writes:
  * [rows][2][N] floats (sum dz | sum dz*z), consumed by yh_bn_bwd_finalize(part, rows, ...).  0: this descriptor
  * cannot take the fused path (the caller keeps the separate yh_bn_silu_bwd_reduce pass). */
-extern "C" int yh_conv_bnr_rows(const yh_conv_desc* d)
-{
-    return conv_desc_plannable(d) && conv_bnr_possible(d) ? conv_rows(d, SIB_BNR) : 0;
-}
+extern "C" int yh_conv_bnr_rows(const yh_conv_desc* d) { yh_conv_plan_info o = {}; yh_conv_info(d, &o); return o.bnr_rows; }
 
 /* diagnostics: a device buffer of grid x 8 x 8 uint64 that receives cycle sums of every workgroup's 2nd tile in conv_halo160_kernel (NULL: off) */
 extern "C" void yh_halo_set_stamps(void* p) { g_halo_stamps = (unsigned long long*)p; }

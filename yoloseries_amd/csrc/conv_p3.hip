@@ -385,23 +385,24 @@ bool p3_plan(const yh_conv_desc* d, P3Plan* pl)
 
 }  // namespace
 
-int yh_p3_rows(const yh_conv_desc* d)
+static int p3_epi(const yh_conv_desc* d) { return d->bnr_part ? 3 : (d->stats ? 1 : 0); }
+
+// entry points used by conv_igemm.hip (yh_conv_igemm with algo 8; common.h): rows and kernel name of the plan / its launch
+int yh_p3_info(const yh_conv_desc* d, ConvSibInfo* out)
 {
     P3Plan pl;
-    return p3_plan(d, &pl) ? pl.gx : 0;
+    if (!(out->rows = p3_plan(d, &pl) ? pl.gx : 0)) return YH_CONV_DECLINED;
+    YH_CHECK_ARG(!d->bnr_part || conv_bnr_operands(d), "yh_conv_igemm: bad fused-reduction operands");
+    snprintf(out->name, sizeof(out->name), "conv_p3_kernel<%d, %d, %d, %d, %d>", pl.ct, pl.kc, p3_epi(d), pl.pt, pl.s);
+    return YH_OK;
 }
 
-int yh_p3_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len)
+int yh_p3_launch(const yh_conv_desc* d, yh_stream stream)
 {
     P3Plan pl;
-    YH_CHECK_ARG(p3_plan(d, &pl), "yh_conv_igemm: algo 8 (3x3 patch kernel) is not eligible for this descriptor");
-    const int epi = d->bnr_part ? 3 : (d->stats ? 1 : 0);
-    if (d->bnr_part)
-        YH_CHECK_ARG(d->bnr_z && yh_aligned16(d->bnr_z) && d->bnr_ldz % 8 == 0 && d->bnr_ws && d->bnr_C >= d->N, "yh_conv_igemm: bad fused-reduction operands");
-    if (name_out) {
-        snprintf(name_out, name_len, "conv_p3_kernel<%d, %d, %d, %d, %d>", pl.ct, pl.kc, epi, pl.pt, pl.s);     // as profilers print it
-        return YH_OK;
-    }
+    if (!p3_plan(d, &pl)) return YH_CONV_DECLINED;
+    YH_CHECK_ARG(!d->bnr_part || conv_bnr_operands(d), "yh_conv_igemm: bad fused-reduction operands");
+    const int epi = p3_epi(d);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(pl.gx, pl.gy), blk(256 * pl.ct);
 #define YH_LAUNCH_P3(CT_, KC_, PT_)                                                                                    \

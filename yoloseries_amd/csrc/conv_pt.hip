@@ -502,8 +502,7 @@ bool pt_plan(const yh_conv_desc* d, PtPlan* pl)
     const unsigned long wb = (unsigned long)d->Npad * Ct * 2;
     if (wb >= lim) return false;
     if (d->nsplit < d->N) return false;                  // one destination (the split store of C3's stacked cba1 | cba2 is an inference form)
-    const bool generic_na = d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res;
-    const bool generic = generic_na || d->accumulate;
+    const bool generic_na = conv_generic_na(d), generic = conv_generic(d);          // (one destination: checked above)
     if (generic && d->stats) return false;
     // 512 / 320 channels: no LDS left for the operand slots of the epilogues that read memory (fused reduction, residual, accumulate);
     // at 512 the weight slice alone is 128 registers
@@ -552,17 +551,19 @@ static unsigned long long* g_pt_stamps = nullptr;
 /* diagnostics: a device buffer of grid x 4 x 8 uint64 that receives shader-clock stamps of every wave's 9th tile (NULL: off) */
 extern "C" void yh_pt_set_stamps(void* p) { g_pt_stamps = (unsigned long long*)p; }
 
-int yh_pt_rows(const yh_conv_desc* d)
+// entry points used by conv_igemm.hip (yh_conv_igemm with algo 13; common.h): rows and kernel name of the plan / its launch
+int yh_pt_info(const yh_conv_desc* d, ConvSibInfo* out)
 {
     PtPlan pl;
-    return pt_plan(d, &pl) ? pl.k.gx : 0;
+    if (!(out->rows = pt_plan(d, &pl) ? pl.k.gx : 0)) return YH_CONV_DECLINED;
+    snprintf(out->name, sizeof(out->name), "conv_pt_kernel<%d, %d, %d>", pl.cs0, pl.cs1, pl.epi);
+    return YH_OK;
 }
 
-int yh_pt_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len)
+int yh_pt_launch(const yh_conv_desc* d, yh_stream stream)
 {
     PtPlan pl;
-    YH_CHECK_ARG(pt_plan(d, &pl), "yh_conv_igemm: algo 13 (training pointwise kernel) is not eligible for this descriptor");
-    if (name_out) { snprintf(name_out, name_len, "conv_pt_kernel<%d, %d, %d>", pl.cs0, pl.cs1, pl.epi); return YH_OK; }
+    if (!pt_plan(d, &pl)) return YH_CONV_DECLINED;
     YH_CHECK_ARG(yh_aligned16(d->seg[0].ptr) && (d->nseg == 1 || yh_aligned16(d->seg[1].ptr)) && yh_aligned16(d->w) && d->out0 && yh_aligned16(d->out0) &&
                  yh_aligned16(d->res) && yh_aligned16(d->bnr_z), "yh_conv_igemm(pt): unaligned operand");
     // timing-only diagnostics (results wrong): YH_PT_ABL bit 0: zero-record input descriptors (every transfer returns zeros without

@@ -255,8 +255,7 @@ bool pw_plan(const yh_conv_desc* d, PwPlan* pl)
     k.N = d->N; k.M = (int)M;
     k.ntiles = (int)((M + tm - 1) / tm);
     k.wbytes = (unsigned)wb;
-    const bool generic = d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->accumulate || d->nsplit < d->N;
-    pl->epi = generic ? 2 : 0;
+    pl->epi = conv_generic(d) ? 2 : 0;
     pl->cin = C;
     pl->gy = d->N / 80;
     int cap = ((C == 320 ? 256 : 512) / pl->gy) & ~7;    // two blocks per CU (one with 320 channels); a multiple of 8: the output-channel groups of a tile share an XCD
@@ -268,17 +267,19 @@ bool pw_plan(const yh_conv_desc* d, PwPlan* pl)
 
 }  // namespace
 
-int yh_pw_rows(const yh_conv_desc* d)
+// entry points used by conv_igemm.hip (yh_conv_igemm with algo 10; common.h): rows and kernel name of the plan / its launch
+int yh_pw_info(const yh_conv_desc* d, ConvSibInfo* out)
 {
     PwPlan pl;
-    return pw_plan(d, &pl) ? pl.gx : 0;
+    if (!(out->rows = pw_plan(d, &pl) ? pl.gx : 0)) return YH_CONV_DECLINED;
+    snprintf(out->name, sizeof(out->name), "conv_pw_kernel<%d, 5, %d, %d>", pl.cin, pl.cin == 80 ? 2 : 1, pl.epi);
+    return YH_OK;
 }
 
-int yh_pw_run(const yh_conv_desc* d, yh_stream stream, char* name_out, int name_len)
+int yh_pw_launch(const yh_conv_desc* d, yh_stream stream)
 {
     PwPlan pl;
-    YH_CHECK_ARG(pw_plan(d, &pl), "yh_conv_igemm: algo 10 (pointwise kernel) is not eligible for this descriptor");
-    if (name_out) { snprintf(name_out, name_len, "conv_pw_kernel<%d, 5, %d, %d>", pl.cin, pl.cin == 80 ? 2 : 1, pl.epi); return YH_OK; }
+    if (!pw_plan(d, &pl)) return YH_CONV_DECLINED;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(pl.gx, pl.gy), blk(256);
 #define YH_LAUNCH_PW(CIN_, TMW_)                                                                                           \
