@@ -403,6 +403,21 @@ int yh_sgd_step(float* p, const float* g, float* buf, const uint8_t* group, int6
  * between replays (warm-up, train_yolov5.py:437-456); at most 3 parameter groups. */
 int yh_sgd_step_dev(float* p, const float* g, float* buf, const uint8_t* group, int64_t n,
                     const float* scal, int nesterov, const float* grad_scale, yh_stream stream);
+/* Adam on a flat arena, torch.optim.Adam semantics (no amsgrad, L2 weight decay folded into the gradient), the second branch of
+ * _init_optimizer (train_yolov5.py:258-280: optim.Adam(params, lr, betas=(momentum, 0.999)) on the same three groups):
+ *   gv = g*grad_scale + wd[group]*p ; m += (1-beta1)*(gv-m) ; v = beta2*v + (1-beta2)*gv*gv ;
+ *   p -= (lr[group]/bc1) * m / (sqrt(v)/sqrt(bc2) + eps),   bc1 = 1 - beta1^t, bc2 = 1 - beta2^t, t = count of THIS step.
+ * Every per-step scalar lives in DEVICE memory, in one block of 16 floats (8-byte aligned):
+ *   blk[0..2] lr | blk[3..5] wd | blk[6] beta1 | blk[7] beta2 | blk[8] eps | blk[9] bc1 | blk[10] sqrt(bc2) | blk[11] reserved |
+ *   blk[12..13] step count t as ONE int64 | blk[14..15] reserved.
+ * The host writes blk[0..8] (and t, when it resumes); yh_adam_advance, in front of the step on the same stream, adds one to t and
+ * writes blk[9] and blk[10], evaluated in double from the betas in the block.  No value of the step is a launch argument, so a
+ * captured hipGraph replays correctly while the host changes lr between replays.  group: one byte per element, NULL = group 0,
+ * bytes above 2 read group 2.  p, g, m, v: any float pointers; 16-byte loads / stores are used where all four share their phase
+ * within 16 bytes (a scalar head and tail around them), the scalar loop otherwise.  grad_scale: device scalar of yh_clip_scale, or NULL. */
+int yh_adam_advance(float* blk, yh_stream stream);
+int yh_adam_step_dev(float* p, const float* g, float* m, float* v, const uint8_t* group, int64_t n,
+                     const float* blk, const float* grad_scale, yh_stream stream);
 /* EMA with the decay read from device memory (trainer/ema_model.py:20-28: the decay ramps with the update count) */
 int yh_ema_update_dev(float* ema, const float* p, int64_t n, const float* decay_dev, yh_stream stream);
 /* advance the device-resident EMA update counter by one and write the decay of this update,

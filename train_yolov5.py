@@ -27,7 +27,7 @@ from config.config import Config                                                
 from yoloseries_amd import models                                                   # noqa: E402
 from yoloseries_amd.loss import YOLOV5Loss                                          # noqa: E402
 from yoloseries_amd.trainer import ExponentialMovingAverageModel, MatchAccumulator, YOLOV5Evaluator   # noqa: E402
-from yoloseries_amd.utils import FlatSGD, mAP_v2                                    # noqa: E402
+from yoloseries_amd.utils import FlatAdam, FlatSGD, mAP_v2                          # noqa: E402
 from yoloseries_amd.utils.dist import (DataParallelGrads, all_reduce_norm, get_local_rank, get_rank, get_world_size,
                                        synchronize)                                # noqa: E402
 from yoloseries_amd.utils.multiscale import draw_multiscale_shape                   # noqa: E402
@@ -173,8 +173,12 @@ class Training:
 
     def _init_optimizer(self):
         """3 parameter groups: BN weights | conv weights (+weight decay) | biases (train_yolov5.py:258-280)"""
-        assert self.hyp['optimizer'].lower() == 'sgd', "the flat-arena optimizer implements SGD-nesterov (the shipped configuration)"
-        return FlatSGD(self.model, lr=self.hyp['lr'], momentum=self.hyp['momentum'], weight_decay=self.hyp['weight_decay'], nesterov=True)
+        kind = str(self.hyp['optimizer']).lower()
+        if kind == 'sgd':
+            return FlatSGD(self.model, lr=self.hyp['lr'], momentum=self.hyp['momentum'], weight_decay=self.hyp['weight_decay'], nesterov=True)
+        if kind == 'adam':
+            return FlatAdam(self.model, lr=self.hyp['lr'], betas=(self.hyp['momentum'], 0.999), weight_decay=self.hyp['weight_decay'])
+        raise ValueError(f"optimizer: {self.hyp['optimizer']!r} is not supported, the choices are 'sgd' and 'adam'")
 
     def _init_scheduler(self):
         """per-epoch LambdaLR factors (train_yolov5.py:152-164)"""
@@ -195,7 +199,8 @@ class Training:
             self.accumulate = max(1, np.interp(step_in_total, xs, [1, hyp['accumulate_loss_step'] / hyp['batch_size'] / get_world_size()]).round())
             for j, g in enumerate(self.optimizer.param_groups):
                 g['lr'] = np.interp(step_in_total, xs, [0., g['initial_lr']] if j != 2 else [hyp['warmup_bias_max_lr'], g['initial_lr']])
-                g['momentum'] = np.interp(step_in_total, xs, [hyp['warmup_momentum'], hyp['momentum']])
+                if 'momentum' in g:               # :453: Adam's groups have none, their betas stay
+                    g['momentum'] = np.interp(step_in_total, xs, [hyp['warmup_momentum'], hyp['momentum']])
 
     # ------------------------------------------------------------------ hot loop (train_yolov5.py:295-375)
     def step(self):
@@ -347,6 +352,8 @@ def main(argv=None, training_cls=None, default_cfg=None):
     ap.add_argument("--batch", type=int)
     ap.add_argument("--steps-per-epoch", type=int)
     ap.add_argument("--model-type")
+    ap.add_argument("--optimizer", choices=["sgd", "adam"], help="overrides the configuration's optimizer key: SGD-nesterov or Adam "
+                    "(betas = (momentum, 0.999)) on the same three parameter groups and the same lr = basic_lr_per_img * batch_size")
     ap.add_argument("--data", choices=["tensor", "dataset", "shapes"], help="tensor: random-noise batches; dataset: synthetic images "
                     "through DataLoader + fixed_imgsize_collate_fn + DataPrefetcher (the reference's data path); shapes: a learnable "
                     "task (coloured rectangles, colour = class) that shows mAP rising")
@@ -380,6 +387,7 @@ def main(argv=None, training_cls=None, default_cfg=None):
     if args.batch: hyp['batch_size'] = args.batch; hyp['accumulate_loss_step'] = args.batch   # noqa: E701,E702
     if args.steps_per_epoch: hyp['steps_per_epoch'] = args.steps_per_epoch  # noqa: E701
     if args.model_type: hyp['model_type'] = args.model_type              # noqa: E701
+    if args.optimizer: hyp['optimizer'] = args.optimizer                 # noqa: E701
     if args.data: hyp['data_source'] = args.data                         # noqa: E701
     if args.device_letterbox:
         if hyp.get('data_source', 'tensor') != 'dataset':

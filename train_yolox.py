@@ -9,6 +9,7 @@ see CLIP_GRAD_NORM).  YOLOXLoss converts the
 target boxes to xywh in place like the reference (loss/yolox_loss.py:70-75): every batch of the loaders is a fresh tensor.
 
     python train_yolox.py [--cfg config/train_yolox.yaml] [--epochs N] [--img 640] [--batch 64] [--data tensor|dataset|shapes]
+                          [--optimizer sgd|adam]
 """
 import os
 import sys

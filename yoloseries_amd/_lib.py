@@ -207,6 +207,8 @@ _SIGS = {
     "yh_gather_f32": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "yh_sgd_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _f32, _i32, _i32, _vp, _vp]),
     "yh_sgd_step_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
+    "yh_adam_advance": (_i32, [_vp, _vp]),
+    "yh_adam_step_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "yh_ema_update_dev": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "yh_ema_advance": (_i32, [_vp, _vp, C.c_double, C.c_double, _vp]),
     "yh_sumsq": (_i32, [_vp, _i64, _vp, _vp, _vp]),

@@ -1,6 +1,6 @@
 // Flat parameter-arena kernels: index-map gather between the fp32 master parameters
 // (PyTorch OIHW layout, state_dict compatible) and the packed bf16 weight images read
-// by the convolution kernels (conv_igemm.hip plans them), plus the optimizer-side streaming kernels (SGD-nesterov with
+// by the convolution kernels (conv_igemm.hip plans them), plus the optimizer-side streaming kernels (SGD-nesterov and Adam with
 // per-element parameter groups, grad-norm, EMA) of train_yolov5.py:258-280,342-350 and
 // trainer/ema_model.py:20-28.  All HBM-bound, one launch per step each.
 #include "common.h"
@@ -89,6 +89,122 @@ __global__ void sgd_dev_kernel(float* __restrict__ p, const float* __restrict__ 
         buf[i] = b;
         float upd = nesterov ? gv + momentum * b : b;
         p[i] = pv - (gi == 0 ? lr[0] : (gi == 1 ? lr[1] : lr[2])) * upd;
+    }
+}
+// ---- Adam (torch.optim.Adam: no amsgrad, L2 weight decay folded into the gradient) ------------------------------------------
+// device block of yh_adam_step_dev / yh_adam_advance, 16 floats (include/yolohip.h):
+//   [0..2] lr | [3..5] wd | [6] beta1 | [7] beta2 | [8] eps | [9] bc1 = 1 - beta1^t | [10] sqrt(1 - beta2^t) | [11] reserved |
+//   [12..13] int64 step count t | [14..15] reserved
+constexpr int ADAM_LR = 0, ADAM_WD = 3, ADAM_B1 = 6, ADAM_B2 = 7, ADAM_EPS = 8, ADAM_BC1 = 9, ADAM_SBC2 = 10, ADAM_T = 12;
+constexpr int ADAM_UNROLL = 2;       // 16-byte chunks per thread and iteration: 8 loads of 16 bytes in flight per lane (88 VGPRs)
+constexpr int ADAM_BLOCKS = 1280;    // 5 workgroups of 4 waves per CU, the resident set at that register count; caps from 768 to none
+                                     // measured inside the process-to-process spread at 7.2 M and 46.6 M elements
+struct AdamConst {
+    float gs, wd[3], step[3], b2, omb1, omb2, sbc2, eps;
+};
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, int gi, const AdamConst& c)
+{
+    gi = gi > 2 ? 2 : gi;
+    const float gv = g * c.gs + (gi == 0 ? c.wd[0] : (gi == 1 ? c.wd[1] : c.wd[2])) * p;
+    m = m + c.omb1 * (gv - m);                               // torch's lerp_(grad, 1 - beta1)
+    v = c.b2 * v + c.omb2 * gv * gv;
+    const float denom = sqrtf(v) / c.sbc2 + c.eps;
+    p = p - (gi == 0 ? c.step[0] : (gi == 1 ? c.step[1] : c.step[2])) * (m / denom);
+}
+__device__ __forceinline__ void adam_chunk(float4& P, const float4& G, float4& M, float4& V, uint32_t gw, const AdamConst& c)
+{
+    adam_elem(P.x, G.x, M.x, V.x, gw & 255, c);
+    adam_elem(P.y, G.y, M.y, V.y, (gw >> 8) & 255, c);
+    adam_elem(P.z, G.z, M.z, V.z, (gw >> 16) & 255, c);
+    adam_elem(P.w, G.w, M.w, V.w, gw >> 24, c);
+}
+// the four group bytes of elements i..i+3 as one word (byte e = element i + e)
+__device__ __forceinline__ uint32_t adam_groups(const uint8_t* __restrict__ group, long i, bool word_ok)
+{
+    if (!group) return 0u;
+    if (word_ok) return *reinterpret_cast<const uint32_t*>(group + i);
+    return (uint32_t)group[i] | ((uint32_t)group[i + 1] << 8) | ((uint32_t)group[i + 2] << 16) | ((uint32_t)group[i + 3] << 24);
+}
+// One streaming pass, 16 B read and 12 B written per element plus the group byte.  Every per-step scalar comes from `blk` (and
+// grad_scale), none from the launch arguments, for the reason given above sgd_dev_kernel.  Layout of the pass: a scalar head up to
+// the first 16-byte boundary of p, 16-byte loads / stores of p, g, m, v from there (ADAM_UNROLL chunks per thread issued before the
+// first use), a scalar tail.  The body needs g, m and v at p's phase within 16 bytes; any other combination runs the scalar loop
+// over all n.  The arithmetic stays scalar fp32 (no packed forms: Makefile, EXACT).
+__global__ __launch_bounds__(TH) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, const uint8_t* __restrict__ group, long n,
+                                                      const float* __restrict__ blk, const float* __restrict__ grad_scale)
+{
+    AdamConst c;
+    c.gs = grad_scale ? *grad_scale : 1.f;
+    const float b1 = blk[ADAM_B1], bc1 = blk[ADAM_BC1];
+    c.b2 = blk[ADAM_B2];
+    c.omb1 = (float)(1.0 - (double)b1);                      // torch rounds the Python double 1 - beta once
+    c.omb2 = (float)(1.0 - (double)c.b2);
+    c.sbc2 = blk[ADAM_SBC2];
+    c.eps = blk[ADAM_EPS];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        c.wd[k] = blk[ADAM_WD + k];
+        c.step[k] = blk[ADAM_LR + k] / bc1;
+    }
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    const uintptr_t ap = reinterpret_cast<uintptr_t>(p);
+    const bool same = ((ap & 3) | (((reinterpret_cast<uintptr_t>(g) ^ ap) | (reinterpret_cast<uintptr_t>(m) ^ ap) |
+                                    (reinterpret_cast<uintptr_t>(v) ^ ap)) & 15)) == 0;
+    long head = same ? (long)(((16 - (ap & 15)) & 15) >> 2) : n;
+    head = head < n ? head : n;
+    for (long i = tid; i < head; i += nth) {
+        float pv = p[i], mv = m[i], vv = v[i];
+        adam_elem(pv, g[i], mv, vv, group ? group[i] : 0, c);
+        p[i] = pv; m[i] = mv; v[i] = vv;
+    }
+    if (!same) return;
+    const long n4 = (n - head) >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p + head);
+    const float4* g4 = reinterpret_cast<const float4*>(g + head);
+    float4* m4 = reinterpret_cast<float4*>(m + head);
+    float4* v4 = reinterpret_cast<float4*>(v + head);
+    const uint8_t* gr = group ? group + head : nullptr;
+    const bool word_ok = (reinterpret_cast<uintptr_t>(gr) & 3) == 0;
+    long ch = tid;
+    for (; ch + (ADAM_UNROLL - 1) * nth < n4; ch += ADAM_UNROLL * nth) {
+        float4 P[ADAM_UNROLL], G[ADAM_UNROLL], M[ADAM_UNROLL], V[ADAM_UNROLL];
+        uint32_t gw[ADAM_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ADAM_UNROLL; ++u) {
+            const long cu = ch + u * nth;
+            P[u] = p4[cu]; G[u] = g4[cu]; M[u] = m4[cu]; V[u] = v4[cu];
+            gw[u] = adam_groups(gr, cu * 4, word_ok);
+        }
+#pragma unroll
+        for (int u = 0; u < ADAM_UNROLL; ++u) {
+            const long cu = ch + u * nth;
+            adam_chunk(P[u], G[u], M[u], V[u], gw[u], c);
+            p4[cu] = P[u]; m4[cu] = M[u]; v4[cu] = V[u];
+        }
+    }
+    for (; ch < n4; ch += nth) {
+        float4 P = p4[ch], M = m4[ch], V = v4[ch];
+        adam_chunk(P, g4[ch], M, V, adam_groups(gr, ch * 4, word_ok), c);
+        p4[ch] = P; m4[ch] = M; v4[ch] = V;
+    }
+    for (long i = head + n4 * 4 + tid; i < n; i += nth) {
+        float pv = p[i], mv = m[i], vv = v[i];
+        adam_elem(pv, g[i], mv, vv, group ? group[i] : 0, c);
+        p[i] = pv; m[i] = mv; v[i] = vv;
+    }
+}
+// the step count of Adam kept on the device, like the EMA's below: one thread advances t and writes the two bias corrections of
+// THIS step, evaluated in double from the betas the block holds (torch: 1 - beta1 ** step, (1 - beta2 ** step) ** 0.5 in Python floats)
+__global__ void adam_advance_kernel(float* __restrict__ blk)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        long long* cnt = reinterpret_cast<long long*>(blk + ADAM_T);
+        const long long t = cnt[0] + 1;
+        cnt[0] = t;
+        const double b1 = (double)blk[ADAM_B1], b2 = (double)blk[ADAM_B2];
+        blk[ADAM_BC1] = (float)(1.0 - pow(b1, (double)t));
+        blk[ADAM_SBC2] = (float)sqrt(1.0 - pow(b2, (double)t));
     }
 }
 __global__ void ema_dev_kernel(float* __restrict__ e, const float* __restrict__ p, long n, const float* __restrict__ decay_dev)
@@ -201,6 +317,25 @@ extern "C" int yh_sgd_step_dev(float* p, const float* g, float* buf, const uint8
     if (n == 0) return YH_OK;
     hipLaunchKernelGGL(sgd_dev_kernel, dim3(grid_for(n)), dim3(TH), 0, (hipStream_t)stream, p, g, buf, group, (long)n, scal, nesterov, grad_scale);
     YH_CHECK_LAUNCH("yh_sgd_step_dev");
+    return YH_OK;
+}
+extern "C" int yh_adam_advance(float* blk, yh_stream stream)
+{
+    YH_CHECK_ARG(blk && (reinterpret_cast<uintptr_t>(blk) & 7) == 0, "yh_adam_advance: bad args (the block is 16 floats, 8-byte aligned)");
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, blk);
+    YH_CHECK_LAUNCH("yh_adam_advance");
+    return YH_OK;
+}
+extern "C" int yh_adam_step_dev(float* p, const float* g, float* m, float* v, const uint8_t* group, int64_t n,
+                                const float* blk, const float* grad_scale, yh_stream stream)
+{
+    YH_CHECK_ARG(p && g && m && v && blk && n >= 0, "yh_adam_step_dev: bad args");
+    if (n == 0) return YH_OK;
+    // one workgroup per TH * ADAM_UNROLL chunks of 16 bytes, capped: a full grid pass is ADAM_BLOCKS * TH * 4 * ADAM_UNROLL elements
+    long blocks = ((long)n / 4 + (long)TH * ADAM_UNROLL - 1) / ((long)TH * ADAM_UNROLL);
+    blocks = blocks > ADAM_BLOCKS ? ADAM_BLOCKS : (blocks < 1 ? 1 : blocks);
+    hipLaunchKernelGGL(adam_dev_kernel, dim3((int)blocks), dim3(TH), 0, (hipStream_t)stream, p, g, m, v, group, (long)n, blk, grad_scale);
+    YH_CHECK_LAUNCH("yh_adam_step_dev");
     return YH_OK;
 }
 extern "C" int yh_ema_update_dev(float* ema, const float* p, int64_t n, const float* decay_dev, yh_stream stream)

@@ -343,6 +343,21 @@ def sgd_step_dev(p, g, buf, group, scal, nesterov, grad_scale=None):
     check(lib().yh_sgd_step_dev(_p(p), _p(g), _p(buf), _p(group), p.numel(), _p(scal), int(nesterov), _p(grad_scale), _st()), "yh_sgd_step_dev")
 
 
+# layout of Adam's device block (include/yolohip.h, yh_adam_step_dev): 16 floats, the step count one int64 at floats 12..13
+ADAM_BLK_FLOATS, ADAM_BLK_HOST, ADAM_BLK_BC1, ADAM_BLK_SBC2, ADAM_BLK_T = 16, 9, 9, 10, 12
+ADAM_GRID_PASS = 1280 * 256 * 4 * 2      # elements of one full grid pass of the step kernel (csrc/arena.hip: ADAM_BLOCKS x TH x 4 x ADAM_UNROLL)
+
+
+def adam_advance(blk):
+    """step count of the device block += 1, bias corrections of that step written into the block"""
+    check(lib().yh_adam_advance(_p(blk), _st()), "yh_adam_advance")
+
+
+def adam_step_dev(p, g, m, v, group, blk, grad_scale=None):
+    """Adam step with lr | wd | betas | eps | bias corrections read from the device block `blk` (16 floats): graph-replay safe"""
+    check(lib().yh_adam_step_dev(_p(p), _p(g), _p(m), _p(v), _p(group), p.numel(), _p(blk), _p(grad_scale), _st()), "yh_adam_step_dev")
+
+
 def ema_update_dev(ema, p, decay_dev):
     check(lib().yh_ema_update_dev(_p(ema), _p(p), p.numel(), _p(decay_dev), _st()), "yh_ema_update_dev")
 

@@ -3,8 +3,8 @@
 A YOLOv5s step enqueues ~700 kernel launches / events through Python + ctypes (4-6 ms of host time): hidden behind the
 GPU at batch 64, the bound at batch 16.  Every entry point of the C ABI only enqueues on the stream it is given — no
 allocation, no synchronisation, no host copies (include/yolohip.h) — and the per-step scalars of the optimizer and of the
-EMA live in device memory (FlatSGD.scal, yh_ema_advance), so the whole step (forward, loss, backward with its side-stream
-branch, clip, SGD, EMA) is captured ONCE into a hipGraph and replayed with one launch per step.
+EMA live in device memory (FlatSGD.scal / FlatAdam.blk, yh_ema_advance), so the whole step (forward, loss, backward with its side-stream
+branch, clip, SGD or Adam, EMA) is captured ONCE into a hipGraph and replayed with one launch per step.
 
     stepper = GraphedStep(step_fn, pre_replay=[opt.graph_pre_replay, ema.graph_pre_replay])
     out = stepper()          # eager for the first `warmup` calls (builds / tunes the programs), then capture, then replay
