@@ -379,6 +379,45 @@ def _conv_plan_table():
     return mod
 
 
+def _conv_rows():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("conv_rows", os.path.join(ROOT, "tools", "conv_rows.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_conv_rows_name_every_instantiation_the_planner_emits():
+    """tools/conv_rows.py, the table tests/test_gpu_conv_instantiations.py runs on the GPU: every row's descriptor is planned to the
+    row's name (rc 0, slab rows where its epilogue writes a slab), its grid_cap column is what the plan does (at batch 64, where the
+    uncapped grid has more than one block), and the rows' names are a superset of every name the planner emits — over the keys of
+    the shipped table with every algo x tile_k x tile_n x grid_cap of conv_plan_table.table_lines, the reduced corpus (shipped
+    choices, 2 000 seeded random descriptors) and the names of tests/golden/conv_plan_digest.json.  An instantiation added without
+    a row fails here, on a machine without a GPU"""
+    import json
+    from yoloseries_amd._lib import lib
+    R, L = _conv_rows(), lib()
+    ids = [r.id for r in R.ROWS]
+    assert len(set(ids)) == len(ids) >= 160
+    for r in R.ROWS:
+        rc, name, stat_rows, bnr_rows = R.plan(L, r.case())
+        assert (rc, name) == (0, r.name), (r.id, rc, name)
+        assert r.B >= 2 and r.N % 8 == 0
+        assert (stat_rows > 0 if r.epi in ("stats", "gstats") else True) and (bnr_rows > 0 if r.epi == "bnr" else True), (r.id, stat_rows, bnr_rows)
+        for cap in (1, 2):
+            assert R.plan(L, r.case(grid_cap=cap))[:2] == (0, r.name), (r.id, cap)          # the cap never changes the instantiation
+        big = [R.plan(L, r.case(B=64, grid_cap=cap))[2] for cap in (0, 1, 2)]
+        assert (big[1] < big[0]) == r.cap, (r.id, big)
+        if r.cap:          # one slab row per block along x: the cap itself (conv_pt_kernel: whole octets of pixel slots)
+            assert big[1:] == ([8, 8] if r.name.startswith("conv_pt_kernel") else [1, 2]), (r.id, big)
+    mod = R.T
+    emitted = set(json.load(open(os.path.join(ROOT, "tests", "golden", "conv_plan_digest.json")))["names"])
+    for lines in (mod.table_lines(L), mod.reduced(L)):
+        emitted |= set(mod.digest(lines)["names"])
+    assert len(emitted) >= 120
+    assert not emitted - {r.name for r in R.ROWS}, sorted(emitted - {r.name for r in R.ROWS})
+
+
 def test_conv_info_agrees_with_the_three_queries():
     """yh_conv_info against yh_conv_kernel_name / yh_conv_stat_blocks / yh_conv_bnr_rows over the reduced corpus of
     tools/conv_plan_table.py (the 530 shipped entries and 2 000 seeded random descriptors, invalid ones included): the same rc, the
