@@ -106,9 +106,7 @@ def _print_kernels(model, key, plan):
     """the kernels every command list of the model's programs resolved to: makes a failing log show what ran"""
     def walk(cmds, into):
         for c in cmds or ():
-            if c[0] == 'pair':
-                walk(c[1], into)
-            elif c[-1][0] != 'sync':
+            if c[-1][0] != 'sync':
                 into[c[-1][0].split('<')[0]] += 1
     for shape, prog in model._yh_state()['progs'].items():
         for what in ("cmd_eval", "cmd_train", "cmd_frozen", "cmd_bwd"):

@@ -8,7 +8,7 @@ import torch
 
 from .. import hipk
 from .._lib import (BnPart, ConvDesc, YH_BN_MAX_PARTS, WgradDesc, YH_CMD_EVENT_RECORD, YH_CMD_STREAM_WAIT, YH_ACT_NONE, YH_CONV_DGRAD,
-                    YoloHipError, check)
+                    YoloHipError)
 from ..hipk import Slice
 from ..streams import side_stream
 from . import flags as _flags
@@ -360,7 +360,6 @@ class BackwardMixin:
                 wd.partial, wd.partial_bytes = self.wg_ws.data_ptr(), self.wg_ws.numel() * 4
         _flags.note_backward_built(self)
         self.cmd_bwd = cmds
-        self.cmd_bwd_frozen = None
         self.bwd_buckets = plan_grad_buckets(marks, pk.gsize, int(os.environ.get("YH_DP_BUCKETS", "4")))
         self.bwd_ready = True
         _tune_cache_save()
@@ -378,108 +377,29 @@ class BackwardMixin:
         with torch.cuda.stream(side):
             return bucket_hook(part)
 
-    def _frozen_bwd_cmds(self):
-        """backward of the evaluation-mode-BatchNorm forward: the same launches, with the batch-mean coefficients every
-        yh_bn_bwd_finalize leaves for the apply pass zeroed (gz = gamma * invstd * dz).  Command indices are preserved
-        for the gradient buckets: the fill rides in the finalize's slot as a pair."""
-        L, out = self.L, []
-        for cmd in self.cmd_bwd:
-            fn = cmd[0]
-            if fn is L.yh_bn_bwd_finalize:
-                coef_ptr = cmd[1][7]
-                out.append(('pair', [cmd, (L.yh_fill_u32, (coef_ptr, 0, 2 * cmd[1][2]), cmd[2], ('yh_fill_u32', 0, 0.0))], cmd[2], ('sync', 0, 0.0)))
-            elif fn is L.yh_bn_bwd_finalize_parts:
-                parts, nparts = cmd[1][0], cmd[1][1]
-                fills = [(L.yh_fill_u32, (parts[i].coef, 0, 2 * int(parts[i].C)), cmd[2], ('yh_fill_u32', 0, 0.0)) for i in range(nparts)]
-                out.append(('pair', [cmd] + fills, cmd[2], ('sync', 0, 0.0)))
-            else:
-                out.append(cmd)
-        return out
-
-    def _compile_backward(self, two, buckets, cmd_bwd=None):
-        """the backward command list as a yh_cmd array: kernels on stream 0 (main) / 1 (side: weight gradients), the event
-        records and stream waits of the gz ring in between; returns (array, positions at which a gradient bucket is complete,
-        per-call patches for the head gradients)"""
-        L = self.L
-        cmd_bwd = self.cmd_bwd if cmd_bwd is None else cmd_bwd
-        cc = CompiledCmds(L, 2 * len(cmd_bwd) + 8 + 4 * sum(1 for c in cmd_bwd if c[0] == 'pair'))
-        cc.source = cmd_bwd
-        breaks, patches = [], []
-        pending = [None] * self.ngz       # per gz buffer: index of the event its last weight-gradient launch recorded
+    def _compile_backward(self, two, buckets, frozen):
+        """compile_backward of this program's command list, on its own events and head-gradient scratch"""
         if two:
             for ev in [self._ev_gz] + self._ev_wg:        # materialise the raw event handles
                 ev.record(self._side)
-            ev_gz, ev_wg = self._ev_gz.cuda_event, [e.cuda_event for e in self._ev_wg]
-        nb = 0
-        for ci, cmd in enumerate(cmd_bwd):
-            while nb < len(buckets) and buckets[nb][0] == ci:
-                breaks.append(cc.n)
-                nb += 1
-            fn = cmd[0]
-            if fn == 'pair':
-                for sub in cmd[1]:
-                    cc.call(sub[0], sub[1], 0, sub[2])
-                continue
-            if fn == 'gz_begin':
-                if two and pending[cmd[1]] is not None:
-                    e = pending[cmd[1]]
-                    cc.event(YH_CMD_STREAM_WAIT, ev_wg[e], 0)
-                    pending = [None if q == e else q for q in pending]
-            elif fn == 'wg_begin':
-                if two:
-                    cc.event(YH_CMD_EVENT_RECORD, ev_gz, 0)
-                    cc.event(YH_CMD_STREAM_WAIT, ev_gz, 1)
-            elif fn == 'wg_end':
-                if two and cmd[1]:
-                    cc.event(YH_CMD_EVENT_RECORD, ev_wg[cmd[1][0]], 1)
-                    for slot in cmd[1]:
-                        pending[slot] = cmd[1][0]
-            elif fn == 'head_colsum':
-                _, op, boff, _m = cmd
-                if boff is not None:
-                    i = cc.call(L.yh_colsum, (0, op.y.C, op.y.C, self.B * op.Ho * op.Wo, self._head_scratch(op, two),
-                                              self.pack.gpack.data_ptr() + 4 * boff), 1 if self._head_on_side(op, two) else 0, op.name)
-                    patches.append(('colsum', None, op.name, i))
-            elif fn == 'wgrad':
-                _, op, wd, _m = cmd
-                if "wgrad" in _flags.ABL_SKIP:
-                    continue
-                cc.call(L.yh_conv_wgrad, (wd,), 1 if two and id(wd) not in self._wgrad_on_main else 0, op.name)
-                if op.kind == 'plain':
-                    patches.append(('wgrad', wd, op.name, -1))
-            elif fn == 'dgrad':
-                _, op, d, _m = cmd
-                cc.call(L.yh_conv_igemm, (d,), 0, op.name)
-                if op.kind == 'plain':
-                    patches.append(('dgrad', d, op.name, -1))
-            else:
-                _, args, name, _m = cmd
-                if fn.__name__ in _flags.ABL_SKIP:
-                    continue
-                cc.call(fn, args, 0, name)
-        while nb < len(buckets):
-            breaks.append(cc.n)
-            nb += 1
-        return cc, breaks, patches
+
+        def colsum_args(op, boff):                        # (argument 0, the head gradient, arrives per call)
+            return (0, op.y.C, op.y.C, self.B * op.Ho * op.Wo, self._head_scratch(op, two), self.pack.gpack.data_ptr() + 4 * boff)
+        return compile_backward(self.L, self.cmd_bwd, two, buckets, frozen, self._ev_gz if two else None, self._ev_wg if two else (),
+                                self._wgrad_on_main, lambda op: self._head_on_side(op, two), colsum_args)
 
     def backward(self, head_grads, bucket_hook=None, frozen=False, param_views=True):
         """head_grads: list of [B,h,w,ld] bf16 gradient buffers matching self.outputs (plain ops).
         bucket_hook(slice of the packed fp32 gradient arena) -> finisher or None: called as soon as a bucket of
         gradients is complete (data-parallel all-reduce overlapped with the remaining backward); finishers run
         before the gradients are scattered to parameter order.
+        frozen: the backward of the evaluation-mode-BatchNorm forward.
         param_views=False: only the flat gradient is wanted (the flat-arena optimizer): the 177 per-parameter views — ~0.5 ms of
         host time between the last backward kernel and the optimizer's first — are not built."""
         if not self.bwd_ready:
             self._build_backward()
-        cmd_bwd = self.cmd_bwd
-        if frozen:
-            if self.cmd_bwd_frozen is None:
-                self.cmd_bwd_frozen = self._frozen_bwd_cmds()
-            cmd_bwd = self.cmd_bwd_frozen
         buckets = self.bwd_buckets if bucket_hook is not None else []
-        nb, finishers = 0, []
-        pk, L = self.pack, self.L
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        pk = self.pack
         hipk.fill_zero(pk.gpack)
         heads = {}
         for o, g in zip(self.outputs, head_grads):
@@ -487,8 +407,8 @@ class BackwardMixin:
                 heads[o.name] = g
             else:
                 o.buf.g[..., o.coff:o.coff + o.C].copy_(g)
-        prof = self.profile
-        two = self.two_streams
+        prof, two = self.profile, self.two_streams
+        main, side = torch.cuda.current_stream(), None
         if two:
             if getattr(self, "_side", None) is None:
                 # a stream PROBED to run beside the compute stream (streams.py: a fresh stream may share its hardware queue)
@@ -496,109 +416,35 @@ class BackwardMixin:
                 self._ev_gz = torch.cuda.Event()
                 self._ev_wg = [torch.cuda.Event() for _ in range(self.ngz)]
                 self._ev_all = torch.cuda.Event()
-            main = torch.cuda.current_stream()
             side = self._side
-            st_side = C.c_void_p(side.cuda_stream)
             self._ev_gz.record(main)               # packed arena zeroed, head gradients in place
             side.wait_event(self._ev_gz)
-            pending = [None] * self.ngz
-        if prof is None and _flags.USE_EXEC:
-            # replay the compiled command array (yh_exec): one call per bucket segment instead of one ctypes call per launch
-            key = ('bwd', two, bucket_hook is not None, frozen)
-            comp = self._compiled.get(key)
-            if comp is None or comp[0].source is not cmd_bwd:
-                comp = self._compiled[key] = self._compile_backward(two, buckets, cmd_bwd)
-            cc, breaks, patches = comp
-            for kind, obj, opname, slot_idx in patches:          # head gradients arrive per call
-                ptr = heads[opname].data_ptr()
-                if kind == 'wgrad':
-                    obj.gy = ptr
-                elif kind == 'dgrad':
-                    obj.seg[0].ptr = ptr
-                else:
-                    cc.arr[slot_idx].slots[0] = ptr
-            streams = [st.value, st_side.value] if two else [st.value]
-            lo = 0
-            for pos in breaks:
-                cc.run(streams, lo, pos)
-                lo = pos
-                finishers.append(self._bucket_ready(bucket_hook, buckets[nb], main if two else None, side if two else None))
-                nb += 1
-            cc.run(streams, lo, cc.n)
-            if two:
-                self._ev_all.record(side)
-                main.wait_event(self._ev_all)
-            for f in finishers:
-                if f is not None:
-                    f()
-            return pk.grads_to_params(param_views)
-        for ci, cmd in enumerate(cmd_bwd):
-            while nb < len(buckets) and buckets[nb][0] == ci:
-                finishers.append(self._bucket_ready(bucket_hook, buckets[nb], main if two else None, side if two else None))
-                nb += 1
-            fn = cmd[0]
-            if fn == 'pair':
-                for sub in cmd[1]:
-                    rc = sub[0](*sub[1], st)
-                    if rc:
-                        check(rc, f"{sub[0].__name__} bwd [{sub[2]}]")
-                continue
-            if fn == 'gz_begin':
-                if two and pending[cmd[1]] is not None:
-                    e = pending[cmd[1]]
-                    main.wait_event(self._ev_wg[e])
-                    pending = [None if q == e else q for q in pending]
-                continue
-            if fn == 'wg_begin':
-                if two:
-                    self._ev_gz.record(main)
-                    side.wait_event(self._ev_gz)
-                continue
-            if fn == 'wg_end':
-                if two and cmd[1]:
-                    self._ev_wg[cmd[1][0]].record(side)
-                    for slot in cmd[1]:
-                        pending[slot] = cmd[1][0]
-                continue
-            on_side = two and ((fn == 'wgrad' and id(cmd[2]) not in self._wgrad_on_main) or 
-                               (fn == 'head_colsum' and self._head_on_side(cmd[1], two)))
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(side if on_side else None)
-            if fn == 'head_colsum':
-                _, op, boff, _m = cmd
-                g = heads[op.name]
-                if boff is not None:
-                    rc = L.yh_colsum(g.data_ptr(), op.y.C, op.y.C, self.B * op.Ho * op.Wo, self._head_scratch(op, two),
-                                     pk.gpack.data_ptr() + 4 * boff, st_side if on_side else st)
-                    if rc:
-                        check(rc, "yh_colsum")
-            elif fn == 'wgrad':
-                _, op, wd, _m = cmd
-                if op.kind == 'plain':
-                    wd.gy = heads[op.name].data_ptr()
-                rc = L.yh_conv_wgrad(C.byref(wd), st_side if on_side else st)
-                if rc:
-                    check(rc, f"yh_conv_wgrad [{op.name}]")
-            elif fn == 'dgrad':
-                _, op, d, _m = cmd
-                if op.kind == 'plain':
-                    d.seg[0].ptr = heads[op.name].data_ptr()
-                rc = L.yh_conv_igemm(C.byref(d), st)
-                if rc:
-                    check(rc, f"yh_conv_igemm dgrad [{op.name}]")
+        key = ('bwd', two, bucket_hook is not None, frozen)
+        comp = self._compiled.get(key)
+        if comp is None or comp[0].source is not self.cmd_bwd:
+            comp = self._compiled[key] = self._compile_backward(two, buckets, frozen)
+        cc, breaks, patches = comp
+        for kind, obj, opname, i in patches:          # head gradients arrive per call
+            ptr = heads[opname].data_ptr()
+            if kind == 'wgrad':
+                obj.gy = ptr
+            elif kind == 'dgrad':
+                obj.seg[0].ptr = ptr
             else:
-                _, args, name, _m = cmd
-                rc = fn(*args, st)
-                if rc:
-                    check(rc, f"{fn.__name__} bwd [{name}]")
-            if prof is not None:
-                e1.record(side if on_side else None)
-                label = cmd[1].name if hasattr(cmd[1], 'name') else cmd[2]
-                prof.setdefault(cmd[3] + (label,), []).append((e0, e1))
-        while nb < len(buckets):
-            finishers.append(self._bucket_ready(bucket_hook, buckets[nb], main if two else None, side if two else None))
-            nb += 1
+                cc.set_arg(i, 0, ptr)
+        streams = [main, side] if two else [main]
+        if prof is None and _flags.USE_EXEC:
+            # replay the compiled array (yh_exec): one call per bucket segment instead of one ctypes call per launch
+            raw = [s.cuda_stream for s in streams]
+            run = lambda lo, hi: cc.run(raw, lo, hi)                        # noqa: E731
+        else:
+            run = lambda lo, hi: cc.run_each(streams, lo, hi, prof)         # noqa: E731
+        lo, finishers = 0, []
+        for pos, bucket in zip(breaks, buckets):
+            run(lo, pos)
+            lo = pos
+            finishers.append(self._bucket_ready(bucket_hook, bucket, main, side))
+        run(lo, cc.n)
         if two:
             self._ev_all.record(side)
             main.wait_event(self._ev_all)
@@ -606,3 +452,70 @@ class BackwardMixin:
             if f is not None:
                 f()
         return pk.grads_to_params(param_views)
+
+
+def compile_backward(L, cmds, two, buckets, frozen, ev_gz, ev_wg, on_main, head_on_side, colsum_args):
+    """The backward command list `cmds` lowered to a yh_cmd array: kernels on stream 0 (main) / 1 (side: weight gradients, head bias
+    gradients), the event records and stream waits of the gz ring in between.  The ONE place that decides streams and
+    synchronisation; both runners of the array (CompiledCmds.run / run_each) follow it.
+    two: the side stream is used (else everything on stream 0, no event entry).  buckets: [(command index, lo, hi)] (plan_grad_buckets).
+    frozen: the backward of the evaluation-mode-BatchNorm forward — the same launches, with the batch-mean coefficients every
+    yh_bn_bwd_finalize leaves for the apply pass zeroed right behind it (gz = gamma * invstd * dz).
+    ev_gz, ev_wg: the event of "gz is ready" and one event per gz buffer (torch.cuda.Events whose handles exist, or bare handles).
+    on_main: ids of the weight-gradient descriptors that stay on the main stream.  head_on_side(op): does a head layer's bias
+    gradient run on the side stream?  colsum_args(op, offset of the bias gradient): its yh_colsum arguments.
+    Returns (array, array positions at which a gradient bucket is complete: the first entry of the bucket's command, per-call
+    patches for the head gradients: (kind, descriptor, op name, entry))."""
+    cc = CompiledCmds(L, (2 + (YH_BN_MAX_PARTS if frozen else 0)) * len(cmds) + 8)      # at most: two events, or a finalize and its fills
+    cc.source = cmds
+    breaks, patches = [], []
+    pending = {}                      # gz buffer -> index of the event its last weight-gradient launch recorded
+    nb = 0
+    for ci, cmd in enumerate(cmds):
+        while nb < len(buckets) and buckets[nb][0] == ci:
+            breaks.append(cc.n)
+            nb += 1
+        fn, meta = cmd[0], cmd[3]
+        if fn == 'gz_begin':          # main stream: wait until this gz buffer's last weight gradient is done
+            e = pending.get(cmd[1])
+            if two and e is not None:
+                cc.event(YH_CMD_STREAM_WAIT, ev_wg[e], 0)
+                pending = {s: q for s, q in pending.items() if q != e}
+        elif fn == 'wg_begin':
+            if two:
+                cc.event(YH_CMD_EVENT_RECORD, ev_gz, 0)
+                cc.event(YH_CMD_STREAM_WAIT, ev_gz, 1)
+        elif fn == 'wg_end':
+            if two and cmd[1]:
+                cc.event(YH_CMD_EVENT_RECORD, ev_wg[cmd[1][0]], 1)
+                for slot in cmd[1]:
+                    pending[slot] = cmd[1][0]
+        elif fn == 'head_colsum':
+            _, op, boff, _m = cmd
+            if boff is not None:
+                i = cc.call(L.yh_colsum, colsum_args(op, boff), 1 if two and head_on_side(op) else 0, op.name, meta)
+                patches.append(('colsum', None, op.name, i))
+        elif fn == 'wgrad':
+            _, op, wd, _m = cmd
+            if "wgrad" in _flags.ABL_SKIP:
+                continue
+            cc.call(L.yh_conv_wgrad, (wd,), 1 if two and id(wd) not in on_main else 0, op.name, meta)
+            if op.kind == 'plain':
+                patches.append(('wgrad', wd, op.name, -1))
+        elif fn == 'dgrad':
+            _, op, d, _m = cmd
+            cc.call(L.yh_conv_igemm, (d,), 0, op.name, meta)
+            if op.kind == 'plain':
+                patches.append(('dgrad', d, op.name, -1))
+        else:
+            _, args, name, _m = cmd
+            if fn.__name__ in _flags.ABL_SKIP:
+                continue
+            cc.call(fn, args, 0, name, meta)
+            if frozen and fn is L.yh_bn_bwd_finalize:
+                cc.call(L.yh_fill_u32, (args[7], 0, 2 * args[2]), 0, name, ('yh_fill_u32', 0, 0.0))
+            elif frozen and fn is L.yh_bn_bwd_finalize_parts:
+                for q in args[0][:args[1]]:
+                    cc.call(L.yh_fill_u32, (q.coef, 0, 2 * int(q.C)), 0, name, ('yh_fill_u32', 0, 0.0))
+    breaks += [cc.n] * (len(buckets) - nb)
+    return cc, breaks, patches

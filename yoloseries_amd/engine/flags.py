@@ -33,10 +33,11 @@ NGZ = int(os.environ.get("YH_GZ_RING", "3"))   # gz buffers the side-stream weig
 SKIP_ALGOS = frozenset(x for x in os.environ.get("YH_SKIP_ALGOS", "").split(",") if x)
 
 # YH_ABL_SKIP=<entry point>[,...|wgrad]: TIMING EXPERIMENTS ONLY (results are wrong) — the named launches are left out of the
-# compiled programs, which gives the wall time a step would have if that family were free (profiles/r03_step_ablation.txt)
+# compiled programs (and so of both their runners), which gives the wall time a step would have if that family were free
+# (profiles/r03_step_ablation.txt)
 ABL_SKIP = frozenset(x for x in os.environ.get("YH_ABL_SKIP", "").split(",") if x)
 
-# YH_EXEC=0: launch every kernel of a program from Python (one ctypes call each) instead of replaying the compiled command array
+# YH_EXEC=0: launch every entry of the compiled command array from Python (one ctypes call each) instead of replaying the array
 # with one yh_exec call (csrc/exec.hip)
 USE_EXEC = os.environ.get("YH_EXEC", "1") != "0"
 

@@ -1,12 +1,11 @@
 """Program, forward side: the inference program (folded BatchNorm + SiLU in the conv epilogue), the training program
 (conv + BatchNorm partial sums -> finalize -> BN+SiLU pass), evaluation-mode BatchNorm under autograd, and running a pass."""
-import ctypes as C
 import os
 
 import torch
 
 from .. import hipk
-from .._lib import BnFoldItem, BnPart, ConvDesc, YH_BN_MAX_PARTS, YH_ACT_NONE, YH_ACT_SILU, YH_CONV_FWD, YoloHipError, check
+from .._lib import BnFoldItem, BnPart, ConvDesc, YH_BN_MAX_PARTS, YH_ACT_NONE, YH_ACT_SILU, YH_CONV_FWD, YoloHipError
 from . import flags as _flags
 from .executor import CompiledCmds
 from .graph import ConvOp, PoolOp, Ref, sppf_chain
@@ -158,7 +157,6 @@ class ForwardMixin:
                 b.t = torch.zeros(B, b.H, b.W, b.C, dtype=torch.bfloat16, device=self.dev)
         self.cmd_train = []
         self.cmd_frozen = None           # derived from cmd_train (evaluation-mode BatchNorm under autograd): rebuilt with it
-        self.cmd_bwd_frozen = None
         skip = set()
         for oi, op in enumerate(self.ops):
             if oi in skip:
@@ -246,33 +244,23 @@ class ForwardMixin:
 
     def _compile(self, cmds):
         cc = CompiledCmds(self.L, len(cmds))
+        cc.source = cmds
         for fn, args, name, meta in cmds:
             if getattr(fn, "__name__", "") in _flags.ABL_SKIP:
                 continue
-            cc.call(fn, args, 0, name)
+            cc.call(fn, args, 0, name, meta)
         return cc
 
     def _run(self, cmds):
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        prof = self.profile
-        if prof is None and _flags.USE_EXEC:
-            key = 'train' if cmds is self.cmd_train else ('frozen' if cmds is getattr(self, "cmd_frozen", None) else 'eval')
-            cc = self._compiled.get(key)
-            if cc is None or cc.source is not cmds:
-                cc = self._compiled[key] = self._compile(cmds)
-                cc.source = cmds
-            cc.run([st.value])
-            return
-        for fn, args, name, meta in cmds:
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            rc = fn(*args, st)
-            if rc != 0:
-                check(rc, f"{getattr(fn, '__name__', fn)} [{name}]")
-            if prof is not None:
-                e1.record()
-                prof.setdefault(meta + (name,), []).append((e0, e1))
+        key = 'train' if cmds is self.cmd_train else ('frozen' if cmds is getattr(self, "cmd_frozen", None) else 'eval')
+        cc = self._compiled.get(key)
+        if cc is None or cc.source is not cmds:
+            cc = self._compiled[key] = self._compile(cmds)
+        main = torch.cuda.current_stream()
+        if self.profile is None and _flags.USE_EXEC:
+            cc.run([main.cuda_stream])
+        else:
+            cc.run_each([main], prof=self.profile)
 
     def _frozen_cmds(self):
         """the training program with every BatchNorm in evaluation mode (model.eval() under autograd): the finalize launches —

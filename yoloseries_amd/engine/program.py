@@ -23,7 +23,9 @@ class Program(ForwardMixin, BackwardMixin, TunerMixin):
                 b.t = torch.zeros(B, b.H, b.W, b.C, dtype=torch.bfloat16, device=dev)
         self.generation = 0
         self.profile = None             # {(kernel family, algorithmic flops): [(start_event, end_event)]} when profiling
-        self._compiled = {}             # 'train' | 'eval' | ('bwd', two_streams, hooked) -> CompiledCmds (yh_exec replay)
+        # the lowered passes, behind both runners (yh_exec replay / one call per launch):
+        # 'train' | 'frozen' | 'eval' -> CompiledCmds;  ('bwd', two_streams, hooked, frozen) -> (CompiledCmds, breaks, patches)
+        self._compiled = {}
         self.bwd_ready = False
         self._keep = []                 # keeps ctypes structs / tensors alive
         self._owned = None              # (state the count was taken in, bytes): owned_bytes()
