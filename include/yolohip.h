@@ -501,6 +501,37 @@ int yh_yolox_loss_fwd(const yh_yolox_desc* d, const void* const* preds, const fl
 int yh_yolox_loss_bwd(const yh_yolox_desc* d, const void* const* preds, const float* targets_xywh, const float* gout,
                       const void* saved, void* const* gpreds, yh_stream stream);
 
+/* ------------------------------------------------------------------------ *
+ * YOLOv8 loss: task-aligned assignment, CIoU, DFL (loss/yolov8_loss.py:12-411)
+ * ------------------------------------------------------------------------ */
+typedef struct yh_v8loss_desc {
+    int32_t B, maxbox, num_class, num_stage;
+    int32_t reg, topk;            /* logits per box side (2..32); cells per ground truth (1..24)                  */
+    int32_t H[4], W[4], ldp[4];   /* per stage: feature map size, elements per cell ([4*reg box, cls...] order)  */
+    int32_t pred_is_f32;
+    float   img_size0;            /* hyp['input_img_size'][0]; stride = img_size0 / H                            */
+    float   alpha, beta;          /* metric = iou^beta * score^alpha                                             */
+    float   focal_gamma, focal_alpha, cls_pos_weight;
+    float   iou_scale, cls_scale, dfl_scale;
+} yh_v8loss_desc;
+/* Valid rows are those with 0 <= class id < num_class.  The 128 valid rows per image that YOLOV8Loss (loss/yolov8_loss.py)
+ * enforces before any launch (it counts rows with class id >= 0 whenever maxbox > 128 and raises YoloHipError) are the
+ * contract it shares with YOLOXLoss, not a capacity of these kernels: there is one workgroup per row, and only the pass that
+ * settles multiply-chosen cells walks an image's rows serially, so its time grows with their number.  Neither buffer scales
+ * with B * maxbox * cells: ws holds 28 bytes per cell and 8 per target row, saved 8 bytes per cell (both 16-byte aligned). */
+size_t yh_v8loss_ws_bytes(const yh_v8loss_desc* d);
+size_t yh_v8loss_saved_bytes(const yh_v8loss_desc* d);
+/* byte offsets inside `saved`: out8[0] = matched target row per cell [B][N] i32 (-1: none), out8[1] = class-target value per
+ * cell [B][N] f32, out8[2] = N, out8[4..7] = first cell of each stage inside an image's N cells */
+int yh_v8loss_layout(const yh_v8loss_desc* d, int64_t* out8);
+/* targets: [B][maxbox][6] (xmin,ymin,xmax,ymax,cls,img) pixels, padding rows cls < 0.
+ * result fp32[8]: tot, cls, iou, dfl, tar_nums (assigned cells), sum of the class targets, 0, 0                       */
+int yh_v8_loss_fwd(const yh_v8loss_desc* d, const void* const* preds, const float* targets, float* result,
+                   void* saved, void* ws, yh_stream stream);
+/* gpreds[s]: same geometry/dtype as preds[s], fully overwritten.  gout: device pointer to d(loss)/d(tot).             */
+int yh_v8_loss_bwd(const yh_v8loss_desc* d, const void* const* preds, const float* targets, const float* gout,
+                   const void* saved, void* const* gpreds, void* ws, yh_stream stream);
+
 /* Box utilities (utils/bbox_tools.py:164-339) fp32.  yh_iou_matrix: (n1, n2) IoU of xyxy boxes; eps_clamp > 0: union clamped from
  * below (gpu_iou, utils/bbox_tools.py:164-190), 0: no clamp on the union (numba_iou :12-35: 0 / 0 = NaN), < 0: no clamp on the
  * intersection sides either (the evaluators' bbox_iou, trainer/eval_yolov5.py:237-258, trainer/eval_yolox.py) */

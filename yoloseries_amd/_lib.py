@@ -106,6 +106,18 @@ class YoloxDesc(C.Structure):
     ]
 
 
+class V8LossDesc(C.Structure):
+    _fields_ = [
+        ("B", C.c_int32), ("maxbox", C.c_int32), ("num_class", C.c_int32), ("num_stage", C.c_int32),
+        ("reg", C.c_int32), ("topk", C.c_int32),
+        ("H", C.c_int32 * 4), ("W", C.c_int32 * 4), ("ldp", C.c_int32 * 4),
+        ("pred_is_f32", C.c_int32), ("img_size0", C.c_float),
+        ("alpha", C.c_float), ("beta", C.c_float),
+        ("focal_gamma", C.c_float), ("focal_alpha", C.c_float), ("cls_pos_weight", C.c_float),
+        ("iou_scale", C.c_float), ("cls_scale", C.c_float), ("dfl_scale", C.c_float),
+    ]
+
+
 class DecodeDesc(C.Structure):
     _fields_ = [
         ("B", C.c_int32), ("num_class", C.c_int32), ("num_anchor", C.c_int32), ("num_stage", C.c_int32),
@@ -224,6 +236,11 @@ _SIGS = {
     "yh_yolox_layout": (_i32, [C.POINTER(YoloxDesc), _vp]),
     "yh_yolox_loss_fwd": (_i32, [C.POINTER(YoloxDesc), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp]),
     "yh_yolox_loss_bwd": (_i32, [C.POINTER(YoloxDesc), C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(_vp), _vp]),
+    "yh_v8loss_ws_bytes": (_sz, [C.POINTER(V8LossDesc)]),
+    "yh_v8loss_saved_bytes": (_sz, [C.POINTER(V8LossDesc)]),
+    "yh_v8loss_layout": (_i32, [C.POINTER(V8LossDesc), _vp]),
+    "yh_v8_loss_fwd": (_i32, [C.POINTER(V8LossDesc), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
+    "yh_v8_loss_bwd": (_i32, [C.POINTER(V8LossDesc), C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(_vp), _vp, _vp]),
     "yh_iou_matrix": (_i32, [_vp, _i32, _vp, _i32, _f32, _vp, _vp]),
     "yh_iou_pairwise": (_i32, [_i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "yh_decode_full": (_i32, [C.POINTER(DecodeDesc), C.POINTER(_vp), _vp, _vp]),

@@ -9,7 +9,7 @@ from .. import _lib
 from .._lib import check, lib
 
 __all__ = ['xyxy2xywh', 'xyxy2xywhn', 'xywh2xyxy', 'numba_xywh2xyxy', 'gpu_iou', 'gpu_Giou', 'gpu_CIoU', 'gpu_DIoU',
-           'numba_iou', 'numba_xyxy2xywh']
+           'numba_iou', 'numba_xyxy2xywh', 'tblr2xyxy', 'xyxy2tblr']
 
 
 def _need_gpu(t, who):
@@ -144,3 +144,20 @@ def gpu_CIoU(bbox1, bbox2):
     if bbox1.shape[0] == 1 and bbox2.shape[0] > 1:          # the reference's expressions broadcast one box against many
         bbox1 = bbox1.expand(bbox2.shape[0], 4)
     return _PairwiseCIoU.apply(bbox1, bbox2).squeeze()
+
+
+def tblr2xyxy(tblr: torch.Tensor, grid: torch.Tensor):
+    """(b, N, 4) distances [t, b, l, r] from the grid points (N, 2) [x, y] -> (b, N, 4) [xmin, ymin, xmax, ymax]
+    (utils/bbox_tools.py:392-407); plain torch, any device"""
+    assert tblr.ndim == 3 and tblr.size(1) == grid.size(0)
+    t, b, l, r = tblr.unbind(-1)
+    gx, gy = grid[:, 0][None], grid[:, 1][None]
+    return torch.stack((gx - l, gy - t, gx + r, gy + b), dim=-1)
+
+
+def xyxy2tblr(xyxy: torch.Tensor, grid: torch.Tensor):
+    """(b, N, 4) [xmin, ymin, xmax, ymax] -> (b, N, 4) distances [t, b, l, r] from the grid points (N, 2) [x, y]
+    (utils/bbox_tools.py:410-426); plain torch, any device"""
+    xmin, ymin, xmax, ymax = xyxy.unbind(-1)
+    gx, gy = grid[:, 0][None], grid[:, 1][None]
+    return torch.stack((gy - ymin, ymax - gy, gx - xmin, xmax - gx), dim=-1)

@@ -79,6 +79,19 @@ def synth_yolox_heads(batch, img_size=640, num_class=80, seed=5, scale=1.0, stri
     return out
 
 
+def synth_v8_heads(batch, img_size=640, num_class=80, reg=16, seed=7, scale=1.0, strides=(4, 8, 16, 32)):
+    """Random YOLOv8 head tensors in the reference layout: OrderedDict pred_xs/s/m/l (or the last len(strides) of them) of
+    (B, 4*reg + nc, h, w) float32 ~ N(0, scale^2).  img_size: int or (h, w)."""
+    from collections import OrderedDict
+    rs = np.random.RandomState(seed)
+    ih, iw = (img_size, img_size) if np.isscalar(img_size) else img_size
+    names = ("pred_xs", "pred_s", "pred_m", "pred_l")[4 - len(strides):]
+    out = OrderedDict()
+    for name, s in zip(names, strides):
+        out[name] = (rs.randn(batch, 4 * reg + num_class, ih // s, iw // s) * scale).astype(np.float32)
+    return out
+
+
 # learnable synthetic detection task: filled rectangles on a dark noisy background, colour = class.  Used by the training
 # drivers (--data shapes) and tests/test_gpu_driver.py to show that the whole stack (forward, loss, backward, optimizer, EMA,
 # evaluator, mAP) LEARNS — random-noise images (synth_targets alone) can only check that it runs.
