@@ -13,7 +13,14 @@ gradient differs from 3.75 x the unit gradient only by the rounding of one more 
 handful of terms): 16 ulp = 2e-6 relative for fp32 gradients; for bf16 gradients both sides are rounded to bf16 once, 2^-8 each.
 
 Not covered: non-square `input_img_size`.  The reference divides x by img_size[0] but takes ds = img_size[1] / fm_w
-(loss/yolov5_loss.py:66) and on a 256 x 128 input either returns NaN or trips its own assertion (:176): no defined behaviour."""
+(loss/yolov5_loss.py:66) and on a 256 x 128 input either returns NaN or trips its own assertion (:176): no defined behaviour.
+
+Saturated logits (test_v5_saturated_logits): objectness and class logits of +30 / -30, where the fp32 sigmoid is exactly 1 or
+1 - sigmoid is exactly 1, so that the focal factor's base (1 - acc) is 0 and its derivative takes the branch that is defined
+to be 0 (csrc/exact_math.h focal_factor).  Same bars as above against the oracle; in addition the gradient of every
+saturated-correct logit is 0 as a value.  The objectness target of a positive is its CIoU, never exactly 1, so the
+saturated-correct sites here are the objectness of cells without a positive at -30 (t = 0) and the target class of a positive
+at +30 (t = class_smooth_factor = 1)."""
 import numpy as np
 import pytest
 import torch
@@ -126,6 +133,69 @@ def test_v5_case_vs_oracle_fresh_seed(dev, name, bf16):
             assert (whole[..., Ct:] == 0).all()
         else:
             np.testing.assert_allclose(gn, ref, rtol=1e-4, atol=1e-4 * np.abs(ref).max())
+
+
+SAT_SPEC = dict(kind="v5", img=128, B=2, stages=3, pscale=1.0, hyp=dict(num_class=3, use_focal_loss=True, focal_loss_gamma=1.5))
+
+
+def saturated_case():
+    """-> (heads, targets): synthetic heads whose objectness and class logits are +30 / -30 in a checkerboard over (row + column +
+    channel); two boxes of class 1 and one padding row per image, sized so that every stage has positives"""
+    heads = lc.heads_of(SAT_SPEC, 1601)
+    E = 5 + SAT_SPEC["hyp"]["num_class"]
+    for h in heads:
+        yy, xx = np.mgrid[0:h.shape[2], 0:h.shape[3]]
+        for ch in range(h.shape[1]):
+            if ch % E >= 4:
+                h[:, ch] = np.where((yy + xx + ch) % 2 == 0, 30.0, -30.0).astype(np.float32)
+    t = np.full((2, 3, 6), -1.0, np.float32)
+    t[0, 0] = [14, 20, 58, 70, 1, 0]
+    t[0, 1] = [60, 36, 118, 110, 1, 0]
+    t[1, 0] = [30, 12, 96, 64, 1, 1]
+    t[1, 2] = [50, 66, 90, 120, 1, 1]          # row 1 of image 1 is the padding row
+    return heads, t
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16cm"])
+def test_v5_saturated_logits(dev, bf16):
+    heads, t = saturated_case()          # +-30 and the targets are exact in bf16; the other logits are rounded for both sides
+    if bf16:
+        heads = [torch.from_numpy(h).to(torch.bfloat16).float().numpy() for h in heads]
+    lf = _loss(SAT_SPEC, dev)
+    preds = _preds(heads, dev, bf16)
+    out = lf(preds, torch.from_numpy(t).to(dev))
+    grads = torch.autograd.grad(out["tot_loss"], preds)
+    of = ov5.V5LossOracle(lc.anchors_of(SAT_SPEC), lc.hyp_of(SAT_SPEC, "cpu"), stage_num=3)
+    opreds = [torch.from_numpy(h).requires_grad_(True) for h in heads]
+    oout = of(opreds, t)
+    ograds = torch.autograd.grad(oout["tot_loss"], opreds)
+    print("saturated", "bf16" if bf16 else "f32", "hip", _items(out), out["tar_nums"], "oracle", _items(oout), oout["tar_nums"])
+    assert out["tar_nums"] == oout["tar_nums"] == _check_assign(lf, SAT_SPEC, t, heads, dev)
+    assert np.isfinite(_items(out)).all()
+    np.testing.assert_allclose(_items(out), _items(oout), rtol=1e-4, atol=1e-6)
+    E = 5 + SAT_SPEC["hyp"]["num_class"]
+    assigned = lf.assign(torch.from_numpy(t).to(dev), [tuple(h.shape[2:]) for h in heads])
+    for s, (gr, og, h) in enumerate(zip(grads, ograds, heads)):
+        ref, gn = og.numpy(), gr.float().cpu().numpy()
+        assert np.isfinite(gn).all()
+        if bf16:
+            np.testing.assert_allclose(gn, ref, rtol=6e-3, atol=1e-3 * np.abs(ref).max())
+        else:
+            np.testing.assert_allclose(gn, ref, rtol=1e-4, atol=1e-4 * np.abs(ref).max())
+        _, cls, img, anc, gy, gx = [a.cpu().numpy() for a in assigned[s]]
+        assert len(cls) > 0
+        obj_at_pos = h[img, anc * E + 4, gy, gx]
+        assert (obj_at_pos == 30).any() and (obj_at_pos == -30).any()
+        # saturated-correct class logits of the positives: t = 1, x = +30
+        hot = h[img, anc * E + 5 + cls, gy, gx] == 30
+        assert hot.any() and (~hot).any()
+        assert (gn[img[hot], (anc * E + 5 + cls)[hot], gy[hot], gx[hot]] == 0).all()
+        # saturated-correct objectness of the cells without a positive: t = 0, x = -30
+        free = np.ones((h.shape[0], 3, h.shape[2], h.shape[3]), bool)
+        free[img, anc, gy, gx] = False
+        obj = h[:, 4::E]
+        assert (gn[:, 4::E][free & (obj == -30)] == 0).all() and (free & (obj == -30)).any()
+        assert (gn[:, 4::E][free & (obj == 30)] != 0).all()
 
 
 def test_v5_hyper_parameters_change_the_result():

@@ -9,7 +9,13 @@ Bars as in test_yolox_loss_vs_oracle_640_b8: foreground masks array-equal (the r
 Oracle-only inputs: 16 / 17 / 128 valid boxes in one image (the matcher's rounds of 16, the 128 boxes held in LDS); 130, which
 YOLOXLoss refuses with an error naming the limit; the reference's randperm fallback (loss/yolox_loss.py:270-278), where the
 kernel's deterministic choice must be one the reference could have drawn and the oracle continues from the same cells; the
-backward scale (see test_gpu_loss_edges.py for its bars)."""
+backward scale (see test_gpu_loss_edges.py for its bars).
+
+Saturated logits (test_yolox_saturated_logits, use_focal_loss on): objectness and class logits of +30 / -30, where the fp32
+sigmoid is exactly 1 or 1 - sigmoid is exactly 1, so that the focal factor's base is 0 and its derivative takes the branch
+defined to be 0 (csrc/exact_math.h focal_factor).  Bars as above; with bf16 heads the oracle runs on the same bf16 values and
+the gradients, stored in bf16, meet test_gpu_loss_edges.py's bf16 bar (rtol 6e-3, atol 1e-3 * max|ref|: half an ulp is 2^-9).  The
+objectness gradient of every saturated-correct cell (foreground at +30, background at -30) is 0 as a value."""
 import numpy as np
 import pytest
 import torch
@@ -35,10 +41,11 @@ def _items(out):
     return np.array([out["tot_loss"].item(), out["iou_loss"], out["l1_loss"], out["cls_loss"], out["cof_loss"]], np.float64)
 
 
-def _vs_oracle(dev, spec, tnp, heads, fallback_cells=None, label=""):
-    """HIP against the stable-tie oracle on one call: masks, counts, items, balances, gradients, in-place target conversion"""
+def _vs_oracle(dev, spec, tnp, heads, fallback_cells=None, label="", bf16=False, seen=None):
+    """HIP against the stable-tie oracle on one call: masks, counts, items, balances, gradients, in-place target conversion.
+    bf16: `heads` hold bf16 values and reach the kernels as bf16 tensors; seen: a dict that receives the masks and gradients"""
     lf = _loss(spec, dev)
-    preds = {k: torch.from_numpy(v).to(dev).requires_grad_(True) for k, v in heads.items()}
+    preds = {k: torch.from_numpy(v).to(dev).to(torch.bfloat16 if bf16 else torch.float32).requires_grad_(True) for k, v in heads.items()}
     t = torch.from_numpy(tnp.copy()).to(dev)
     out = lf(preds, t)
     masks = lf.foreground_masks()
@@ -58,10 +65,15 @@ def _vs_oracle(dev, spec, tnp, heads, fallback_cells=None, label=""):
     grads = torch.autograd.grad(out["tot_loss"], list(preds.values()))
     ograds = torch.autograd.grad(oout["tot_loss"], list(opreds.values()))
     for gr, og in zip(grads, ograds):
-        r, gn = og.numpy(), gr.cpu().numpy()
+        r, gn = og.numpy(), gr.float().cpu().numpy()
         assert np.isfinite(gn).all()
-        np.testing.assert_allclose(gn, r, rtol=1e-4, atol=1e-4 * np.abs(r).max())
+        if bf16:
+            np.testing.assert_allclose(gn, r, rtol=6e-3, atol=1e-3 * np.abs(r).max())
+        else:
+            np.testing.assert_allclose(gn, r, rtol=1e-4, atol=1e-4 * np.abs(r).max())
     assert np.isfinite(out["tot_loss"].item())
+    if seen is not None:
+        seen.update(masks=masks, grads=[g.float().cpu().numpy() for g in grads])
     return of
 
 
@@ -103,6 +115,42 @@ def test_yolox_case_vs_oracle_fresh_seed(dev, name):
     of = _vs_oracle(dev, spec, _G[f"{name}_f_targets"], lc.heads_of(spec, spec["fresh_seed"]), label=name)
     if name == "x_radius025":
         assert of.counters["ctr_is_box"] > 0
+
+
+SAT_SPEC = dict(kind="yolox", img=128, B=2, hyp=dict(num_class=3, use_focal_loss=True, focal_loss_gamma=1.5))
+
+
+def saturated_case():
+    """-> (heads, targets): synthetic heads whose objectness and class logits are +30 / -30 in a checkerboard over (row + column +
+    channel); two boxes and one padding row per image"""
+    heads = lc.heads_of(SAT_SPEC, 1602)
+    for h in heads.values():
+        yy, xx = np.mgrid[0:h.shape[3], 0:h.shape[4]]
+        for ch in range(4, h.shape[2]):
+            h[:, 0, ch] = np.where((yy + xx + ch) % 2 == 0, 30.0, -30.0).astype(np.float32)
+    t = np.full((2, 3, 6), -1.0, np.float32)
+    t[0, 0] = [14, 20, 58, 70, 1, 0]
+    t[0, 1] = [60, 36, 118, 110, 2, 0]
+    t[1, 0] = [30, 12, 96, 64, 0, 1]
+    t[1, 2] = [50, 66, 90, 120, 1, 1]          # row 1 of image 1 is the padding row
+    return heads, t
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+def test_yolox_saturated_logits(dev, bf16):
+    heads, t = saturated_case()          # +-30 and the targets are exact in bf16; the other logits are rounded for both sides
+    if bf16:
+        heads = {k: torch.from_numpy(v).to(torch.bfloat16).float().numpy() for k, v in heads.items()}
+    seen = {}
+    _vs_oracle(dev, SAT_SPEC, t, heads, label="saturated bf16" if bf16 else "saturated f32", bf16=bf16, seen=seen)
+    met = set()          # objectness logits of the foreground cells, over the stages (the 4 x 4 map has three such cells)
+    for h, fg, gn in zip(heads.values(), seen["masks"], seen["grads"]):
+        obj, gobj = h[:, 0, 4].reshape(-1), gn[:, 0, 4].reshape(-1)
+        met |= set(obj[fg].tolist())
+        assert (gobj[fg & (obj == 30)] == 0).all()          # t = 1, x = +30
+        assert (gobj[~fg & (obj == -30)] == 0).all()         # t = 0, x = -30
+        assert (gobj[fg & (obj == -30)] != 0).all() and (gobj[~fg & (obj == 30)] != 0).all()
+    assert met == {30.0, -30.0}
 
 
 def test_yolox_hyper_parameters_change_the_result():

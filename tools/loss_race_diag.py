@@ -35,8 +35,8 @@ def worker(rank, iters, q, mode="random", done=None):
     chk = {"saved": 0, "pred": 0, "n": 0}
     if mode == "model_full":
         # are the loss's inputs at BACKWARD time what they were at the end of its forward?
-        from yoloseries_amd.loss import yolov5_loss as yl
-        f0, b0 = yl._V5LossFn.forward, yl._V5LossFn.backward
+        from yoloseries_amd.loss import _base as yl
+        f0, b0 = yl.LossFn.forward, yl.LossFn.backward
         def fwd(ctx, owner, targets, *preds):
             r = f0(ctx, owner, targets, *preds)
             ctx.saved0 = ctx.saved.clone()
@@ -47,8 +47,8 @@ def worker(rank, iters, q, mode="random", done=None):
             chk["saved"] += int(not torch.equal(ctx.saved0, ctx.saved))
             chk["pred"] += sum(int(not torch.equal(c0, c)) for c0, c in zip(ctx.canon0, ctx.canon))
             return b0(ctx, *a)
-        yl._V5LossFn.forward = staticmethod(fwd)
-        yl._V5LossFn.backward = staticmethod(bwd)
+        yl.LossFn.forward = staticmethod(fwd)
+        yl.LossFn.backward = staticmethod(bwd)
     if mode != "random":
         from yoloseries_amd import models
         torch.manual_seed(0)

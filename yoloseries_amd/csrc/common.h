@@ -110,6 +110,10 @@ inline void yh_lds_limit(YhDevOnce& once, std::initializer_list<YhLdsLimit> limi
 
 static inline bool yh_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
+// the element type of the head tensors (desc.pred_is_f32) as a type: f(float()) or f(uint16_t()) (bf16), so that a launch
+// of a kernel<T> is written once:  yh_pred_type(d->pred_is_f32, [&](auto e) { using T = decltype(e); ... kernel<T> ... });
+template <typename F> inline void yh_pred_type(int is_f32, F&& f) { if (is_f32) f(float()); else f(uint16_t()); }
+
 // an epilogue of a conv beyond the plain store: affine / activation / residual / second destination (_na: accumulation aside)
 inline bool conv_generic_na(const yh_conv_desc* d) { return d->bias || d->scale || d->shift || d->act != YH_ACT_NONE || d->res || d->nsplit < d->N; }
 inline bool conv_generic(const yh_conv_desc* d) { return conv_generic_na(d) || d->accumulate; }

@@ -10,7 +10,7 @@
 //   backward — obj_bwd streams the whole gradient tensor once (zeros + objectness grads),
 //              pos_bwd overwrites the (5+nc) channels of cells that own positives.
 // Predictions are NHWC (cell-major) [B][H][W][ld] with channel a*(5+nc)+e, bf16 or fp32.
-#include "common.h"
+#include "exact_math.h"
 
 namespace {
 
@@ -151,101 +151,6 @@ __global__ __launch_bounds__(1024) void v5_assign_kernel(const LossK p, const fl
     if (t == 0) count[s] = base_s;
 }
 
-// ---------------------------------------------------------------- math helpers
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// BCEWithLogits(x, t, pos_weight) as torch computes it, and d/dx
-__device__ __forceinline__ float bce_logits(float x, float t, float pw, float* dx) {
-    const float lw = 1.0f + (pw - 1.0f) * t;
-    const float sp = log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.0f);     // softplus(-x)
-    const float sg = sigm(x);
-    if (dx) *dx = (1.0f - t) - lw * (1.0f - sg);
-    return (1.0f - t) * x + lw * sp;
-}
-// focal factor (:216-235) and d/dx
-__device__ __forceinline__ float focal_factor(float x, float t, float gamma, float alpha, float* dx) {
-    const float pr = sigm(x);
-    const float acc = t * pr + (1.0f - t) * (1.0f - pr);
-    const float one_m = 1.0f - acc;
-    const float gf = powf(one_m, gamma);
-    const float af = t * alpha + (1.0f - t) * (1.0f - alpha);
-    if (dx) {
-        // d(1-acc)/dx = -(2t-1) p(1-p)
-        const float dgf = (one_m > 0.f) ? gamma * powf(one_m, gamma - 1.0f) * (-(2.0f * t - 1.0f) * pr * (1.0f - pr)) : 0.f;
-        *dx = dgf * af;
-    }
-    return gf * af;
-}
-
-// CIoU of xyxy boxes (utils/bbox_tools.py:286-339) + gradient w.r.t. b1, alpha constant
-__device__ float ciou_fwd_bwd(const float* b1, const float* b2, float* g /*4 or null*/)
-{
-    const float eps = 1e-9f;
-    const float x1 = b1[0], y1 = b1[1], x2 = b1[2], y2 = b1[3];
-    const float X1 = b2[0], Y1 = b2[1], X2 = b2[2], Y2 = b2[3];
-    const float w1 = x2 - x1, h1 = y2 - y1, w2 = X2 - X1, h2 = Y2 - Y1;
-    const float ixmax = fminf(x2, X2), ixmin = fmaxf(x1, X1);
-    const float iymax = fminf(y2, Y2), iymin = fmaxf(y1, Y1);
-    const float iwr = ixmax - ixmin, ihr = iymax - iymin;
-    const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
-    const float inter = iw * ih;
-    const float union_raw = w1 * h1 + w2 * h2 - inter;
-    const float uni = fmaxf(union_raw, eps);
-    const float iou = inter / uni;
-    const float cxmin = fminf(x1, X1), cxmax = fmaxf(x2, X2);
-    const float cymin = fminf(y1, Y1), cymax = fmaxf(y2, Y2);
-    const float c_hs = cymax - cymin, c_ws = cxmax - cxmin;
-    const float cd_raw = c_ws * c_ws + c_hs * c_hs;
-    const float c1x = (x1 + x2) / 2.f, c1y = (y1 + y2) / 2.f;
-    const float c2x = (X1 + X2) / 2.f, c2y = (Y1 + Y2) / 2.f;
-    const float ctr_ws = c1x - c2x, ctr_hs = c1y - c2y;
-    const float ctr = ctr_hs * ctr_hs + ctr_ws * ctr_ws;
-    const float kk = (float)(4.0 / (3.14159265358979323846 * 3.14159265358979323846));
-    const float h1c = fmaxf(h1, eps), h2c = fmaxf(h2, eps);
-    const float u1 = w1 / h1c;
-    const float dA = atanf(u1) - atanf(w2 / h2c);
-    const float v = kk * dA * dA;
-    const float alpha = v / fmaxf(1.f - iou + v, eps);
-    const float cd = fmaxf(cd_raw, eps);
-    const float ciou = iou - (ctr / cd + v * alpha);
-    if (g) {
-        // order of unknowns: x1, y1, x2, y2
-        // torch.min/max split the gradient evenly on ties (minimum/maximum backward); clamp(min=0) passes at >= 0
-        auto lt = [](float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); };
-        const float pw_ = (iwr >= 0.f) ? 1.f : 0.f, ph_ = (ihr >= 0.f) ? 1.f : 0.f;
-        const float diw[4] = {-pw_ * lt(X1, x1), 0.f, pw_ * lt(x2, X2), 0.f};
-        const float dih[4] = {0.f, -ph_ * lt(Y1, y1), 0.f, ph_ * lt(y2, Y2)};
-        const float dw1[4] = {-1.f, 0.f, 1.f, 0.f};
-        const float dh1[4] = {0.f, -1.f, 0.f, 1.f};
-        const float dcw[4] = {-lt(x1, X1), 0.f, lt(X2, x2), 0.f};
-        const float dch[4] = {0.f, -lt(y1, Y1), 0.f, lt(Y2, y2)};
-        const float dcx[4] = {0.5f, 0.f, 0.5f, 0.f};
-        const float dcy[4] = {0.f, 0.5f, 0.f, 0.5f};
-        const float du_dw = 1.f / h1c;
-        const float du_dh = (h1 >= eps) ? -w1 / (h1c * h1c) : 0.f;
-        const float datan = 1.f / (1.f + u1 * u1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float dinter = ih * diw[i] + iw * dih[i];
-            const float dunion = (union_raw >= eps) ? (dw1[i] * h1 + w1 * dh1[i] - dinter) : 0.f;
-            const float diou = (dinter * uni - inter * dunion) / (uni * uni);
-            const float dcd = (cd_raw >= eps) ? (2.f * c_ws * dcw[i] + 2.f * c_hs * dch[i]) : 0.f;
-            const float dctr = 2.f * ctr_ws * dcx[i] + 2.f * ctr_hs * dcy[i];
-            const float dterm = (dctr * cd - ctr * dcd) / (cd * cd);
-            const float dv = 2.f * kk * dA * datan * (du_dw * dw1[i] + du_dh * dh1[i]);
-            g[i] = diou - dterm - alpha * dv;
-        }
-    }
-    return ciou;
-}
-
-template <typename T> __device__ __forceinline__ float ldp(const T* p);
-template <> __device__ __forceinline__ float ldp<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float ldp<uint16_t>(const uint16_t* p) { return bf2f(*p); }
-template <typename T> __device__ __forceinline__ void stp(T* p, float v);
-template <> __device__ __forceinline__ void stp<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void stp<uint16_t>(uint16_t* p, float v) { *p = f2bf(v); }
-
 struct Stage {
     const void* pred;
     void* gpred;
@@ -293,7 +198,7 @@ __global__ __launch_bounds__(256) void v5_pos_fwd_kernel(const LossK p, const St
     const int E = 5 + d.num_class;
     const int t = threadIdx.x, sub = t & 15, grp = t >> 4;
     const T* pred = reinterpret_cast<const T*>(st.pred);
-    double acc_iou = 0.0, acc_cls = 0.0;
+    double acc[2] = {0.0, 0.0};          // iou, class
     for (int n = blockIdx.x * 16 + grp; n < N; n += gridDim.x * 16) {
         const int32_t* ii = tidx + ((size_t)s * p.L.cap + n) * 5;
         const float* tb = tbox + ((size_t)s * p.L.cap + n) * 4;
@@ -302,7 +207,7 @@ __global__ __launch_bounds__(256) void v5_pos_fwd_kernel(const LossK p, const St
         const T* row = pred + (((size_t)img * st.H + gy) * st.W + gx) * st.ld + anc * E;
         float lg[4];
         {
-            float mine = (sub < 4) ? ldp<T>(row + sub) : 0.f;
+            float mine = (sub < 4) ? ldf<T>(row + sub) : 0.f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) lg[i] = __shfl(mine, i, 16);
         }
@@ -310,10 +215,10 @@ __global__ __launch_bounds__(256) void v5_pos_fwd_kernel(const LossK p, const St
         float cls_sum = 0.f;
         if (d.num_class > 1) {
             for (int e = 5 + sub; e < E; e += 16) {
-                const float x = ldp<T>(row + e);
+                const float x = ldf<T>(row + e);
                 const float tt = (e - 5 == cls) ? d.cls_smooth : 0.f;
-                float l = bce_logits(x, tt, d.cls_pos_weight, nullptr);
-                if (d.use_focal) l *= focal_factor(x, tt, d.focal_gamma, d.focal_alpha, nullptr);
+                float l = bce_logits(x, tt, d.cls_pos_weight, nullptr, nullptr);
+                if (d.use_focal) l *= focal_factor(x, tt, d.focal_gamma, d.focal_alpha, nullptr, nullptr);
                 cls_sum += l;
             }
 #pragma unroll
@@ -321,20 +226,17 @@ __global__ __launch_bounds__(256) void v5_pos_fwd_kernel(const LossK p, const St
         }
         if (sub == 0) {
             ciou_out[(size_t)s * p.L.cap + n] = c;
-            acc_iou += (double)(1.0f - c);
-            acc_cls += (double)cls_sum;
+            acc[0] += (double)(1.0f - c);
+            acc[1] += (double)cls_sum;
             const int cell = ((img * d.num_anchor + anc) * st.H + gy) * st.W + gx;
             const int prev = atomicExch(head + p.L.head_off[s] + cell, n);
             next[(size_t)s * p.L.cap + n] = prev;
         }
     }
-    acc_iou = wave_sum_d(acc_iou);
-    acc_cls = wave_sum_d(acc_cls);
-    if ((t & 63) == 0) { sred[0][t >> 6] = acc_iou; sred[1][t >> 6] = acc_cls; }
-    __syncthreads();
+    block_partials(acc, sred);
     if (t == 0) {
-        part[((size_t)s * 3 + 0) * PART_BLOCKS + blockIdx.x] = sred[0][0] + sred[0][1] + sred[0][2] + sred[0][3];
-        part[((size_t)s * 3 + 1) * PART_BLOCKS + blockIdx.x] = sred[1][0] + sred[1][1] + sred[1][2] + sred[1][3];
+        part[((size_t)s * 3 + 0) * PART_BLOCKS + blockIdx.x] = block_total(sred[0]);
+        part[((size_t)s * 3 + 1) * PART_BLOCKS + blockIdx.x] = block_total(sred[1]);
     }
 }
 
@@ -352,7 +254,7 @@ __global__ __launch_bounds__(256) void v5_obj_fwd_kernel(const LossK p, const St
                                                          double* __restrict__ part)
 {
     const Stage st = sts.s[blockIdx.y];          // one launch for all stages: they are independent of each other
-    __shared__ double sred[4];
+    __shared__ double sred[1][4];
     const yh_v5loss_desc& d = p.d;
     const int s = st.s, A = d.num_anchor, E = 5 + d.num_class;
     const int ncell = p.L.ncell[s];
@@ -360,7 +262,7 @@ __global__ __launch_bounds__(256) void v5_obj_fwd_kernel(const LossK p, const St
     const int32_t* hd = head + p.L.head_off[s];
     const int32_t* nx = next + (size_t)s * p.L.cap;
     const float* ci = ciou + (size_t)s * p.L.cap;
-    double acc = 0.0;
+    double acc[1] = {0.0};
     // thread index enumerates (img, y, x, a) with a fastest so that neighbouring lanes share cache lines
     for (int id = blockIdx.x * blockDim.x + threadIdx.x; id < ncell; id += gridDim.x * blockDim.x) {
         const int a = id % A;
@@ -369,18 +271,16 @@ __global__ __launch_bounds__(256) void v5_obj_fwd_kernel(const LossK p, const St
         const int r2 = pix / st.W;
         const int y = r2 % st.H;
         const int img = r2 / st.H;
-        const float lg = ldp<T>(pred + (size_t)pix * st.ld + a * E + 4);
+        const float lg = ldf<T>(pred + (size_t)pix * st.ld + a * E + 4);
         const int h = hd[((img * A + a) * st.H + y) * st.W + x];
         float tt = 0.f;
         if (h >= 0) tt = fmaxf(ci[list_max(nx, h)], 0.f);
-        float l = bce_logits(lg, tt, d.cof_pos_weight, nullptr);
-        if (d.use_focal) l *= focal_factor(lg, tt, d.focal_gamma, d.focal_alpha, nullptr);
-        acc += (double)l;
+        float l = bce_logits(lg, tt, d.cof_pos_weight, nullptr, nullptr);
+        if (d.use_focal) l *= focal_factor(lg, tt, d.focal_gamma, d.focal_alpha, nullptr, nullptr);
+        acc[0] += (double)l;
     }
-    acc = wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[((size_t)s * 3 + 2) * PART_BLOCKS + blockIdx.x] = sred[0] + sred[1] + sred[2] + sred[3];
+    block_partials(acc, sred);
+    if (threadIdx.x == 0) part[((size_t)s * 3 + 2) * PART_BLOCKS + blockIdx.x] = block_total(sred[0]);
 }
 
 // ---------------------------------------------------------------- finalize
@@ -470,13 +370,13 @@ __global__ __launch_bounds__(256) void v5_obj_bwd_kernel(const LossK p, const St
                 const int r2 = pix / st.W;
                 const int y = r2 % st.H;
                 const int img = r2 / st.H;
-                const float lg = ldp<T>(pred + (size_t)pix * st.ld + a * E + 4);
+                const float lg = ldf<T>(pred + (size_t)pix * st.ld + a * E + 4);
                 const int h = hd[((img * A + a) * st.H + y) * st.W + x];
                 float tt = 0.f;
                 if (h >= 0) tt = fmaxf(ci[list_max(nx, h)], 0.f);
                 float dl, df = 0.f, f = 1.f;
-                const float l = bce_logits(lg, tt, d.cof_pos_weight, &dl);
-                if (d.use_focal) f = focal_factor(lg, tt, d.focal_gamma, d.focal_alpha, &df);
+                const float l = bce_logits(lg, tt, d.cof_pos_weight, &dl, nullptr);
+                if (d.use_focal) f = focal_factor(lg, tt, d.focal_gamma, d.focal_alpha, &df, nullptr);
                 gv = coef * (dl * f + l * df);
             }
             sG[pl * 4 + a] = gv;
@@ -539,7 +439,7 @@ __global__ __launch_bounds__(256) void v5_pos_bwd_kernel(const LossK p, const St
         const T* row = pred + roff;
         float lg[4];
         {
-            float mine = (sub < 4) ? ldp<T>(row + sub) : 0.f;
+            float mine = (sub < 4) ? ldf<T>(row + sub) : 0.f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) lg[i] = __shfl(mine, i, 16);
         }
@@ -564,11 +464,11 @@ __global__ __launch_bounds__(256) void v5_pos_bwd_kernel(const LossK p, const St
                 float gv = 0.f;
                 if (e < 4) gv = kbox * dl4[e];
                 else if (e >= 5 && d.num_class > 1) {
-                    const float x = ldp<T>(row + e);
+                    const float x = ldf<T>(row + e);
                     const float tt = (e - 5 == cls) ? d.cls_smooth : 0.f;
                     float dl, df = 0.f, f = 1.f;
-                    const float l = bce_logits(x, tt, d.cls_pos_weight, &dl);
-                    if (d.use_focal) f = focal_factor(x, tt, d.focal_gamma, d.focal_alpha, &df);
+                    const float l = bce_logits(x, tt, d.cls_pos_weight, &dl, nullptr);
+                    if (d.use_focal) f = focal_factor(x, tt, d.focal_gamma, d.focal_alpha, &df, nullptr);
                     gv = kcls * (dl * f + l * df);
                 }
                 if (slot < 8) gacc[slot] += gv;
@@ -576,7 +476,7 @@ __global__ __launch_bounds__(256) void v5_pos_bwd_kernel(const LossK p, const St
         }
         int slot = 0;
         for (int e = sub; e < E; e += 16, ++slot)
-            if (e != 4 && slot < 8) stp<T>(gp + roff + e, gacc[slot]);
+            if (e != 4 && slot < 8) stf<T>(gp + roff + e, gacc[slot]);
     }
 }
 
@@ -592,6 +492,15 @@ int check_desc(const yh_v5loss_desc* d, const char* who) {
     }
     YH_CHECK_ARG((long)5 * d->num_anchor * d->B * d->maxbox < (1L << 28), "%s: too many targets", who);
     return YH_OK;
+}
+
+// the four stage slots of a launch; slots past num_stage repeat stage 0 and are never indexed (gridDim.y = num_stage)
+void fill_stages(const yh_v5loss_desc* d, const void* const* preds, void* const* gpreds, Stages& all) {
+    for (int s = 0; s < 4; ++s) {
+        const int q = s < d->num_stage ? s : 0;
+        Stage& sg = all.s[s];
+        sg.pred = preds[q]; sg.gpred = gpreds ? gpreds[q] : nullptr; sg.s = q; sg.H = d->H[q]; sg.W = d->W[q]; sg.ld = d->ldp[q];
+    }
 }
 
 }  // namespace
@@ -654,19 +563,13 @@ extern "C" int yh_v5_loss_fwd(const yh_v5loss_desc* d, const void* const* preds,
     if (nb_pos > PART_BLOCKS) nb_pos = PART_BLOCKS;
     int nb_obj = PART_BLOCKS;
     Stages all;
-    for (int s = 0; s < 4; ++s) {
-        const int q = s < d->num_stage ? s : 0;
-        Stage& sg = all.s[s];
-        sg.pred = preds[q]; sg.gpred = nullptr; sg.s = q; sg.H = d->H[q]; sg.W = d->W[q]; sg.ld = d->ldp[q];
-    }
+    fill_stages(d, preds, nullptr, all);
     // positives of every stage, then the objectness pass of every stage (it reads the stage's CIoU values): two launches
-    if (d->pred_is_f32) {
-        hipLaunchKernelGGL((v5_pos_fwd_kernel<float>), dim3(nb_pos, d->num_stage), dim3(256), 0, st, k, all, count, tbox, tidx, ciou, next, head, part);
-        hipLaunchKernelGGL((v5_obj_fwd_kernel<float>), dim3(nb_obj, d->num_stage), dim3(256), 0, st, k, all, ciou, next, head, part);
-    } else {
-        hipLaunchKernelGGL((v5_pos_fwd_kernel<uint16_t>), dim3(nb_pos, d->num_stage), dim3(256), 0, st, k, all, count, tbox, tidx, ciou, next, head, part);
-        hipLaunchKernelGGL((v5_obj_fwd_kernel<uint16_t>), dim3(nb_obj, d->num_stage), dim3(256), 0, st, k, all, ciou, next, head, part);
-    }
+    yh_pred_type(d->pred_is_f32, [&](auto e) {
+        using T = decltype(e);
+        hipLaunchKernelGGL((v5_pos_fwd_kernel<T>), dim3(nb_pos, d->num_stage), dim3(256), 0, st, k, all, count, tbox, tidx, ciou, next, head, part);
+        hipLaunchKernelGGL((v5_obj_fwd_kernel<T>), dim3(nb_obj, d->num_stage), dim3(256), 0, st, k, all, ciou, next, head, part);
+    });
     hipLaunchKernelGGL(v5_finalize_kernel, dim3(1), dim3(1024), 0, st, k, count, part, nb_pos, nb_obj, balances, bal_used, result);
     YH_CHECK_LAUNCH("yh_v5_loss_fwd");
     return YH_OK;
@@ -694,101 +597,18 @@ extern "C" int yh_v5_loss_bwd(const yh_v5loss_desc* d, const void* const* preds,
     Stages all;
     long ntile_max = 1;
     for (int s = 0; s < d->num_stage; ++s) YH_CHECK_ARG(preds[s] && gpreds[s] && yh_aligned16(gpreds[s]), "yh_v5_loss_bwd: stage %d pointers null/unaligned", s);
-    for (int s = 0; s < 4; ++s) {
-        const int q = s < d->num_stage ? s : 0;
-        Stage& sg = all.s[s];
-        sg.pred = preds[q]; sg.gpred = gpreds[q]; sg.s = q; sg.H = d->H[q]; sg.W = d->W[q]; sg.ld = d->ldp[q];
-        const long ntile = ((long)d->B * sg.H * sg.W + 63) / 64;
-        if (s < d->num_stage && ntile > ntile_max) ntile_max = ntile;
+    fill_stages(d, preds, gpreds, all);
+    for (int s = 0; s < d->num_stage; ++s) {
+        const long ntile = ((long)d->B * d->H[s] * d->W[s] + 63) / 64;
+        if (ntile > ntile_max) ntile_max = ntile;
     }
     const int gb = (int)(ntile_max > 4096 ? 4096 : ntile_max);
     // the objectness pass writes every stage's whole gradient tensor, then the positives fill their channels: two launches
-    if (d->pred_is_f32) {
-        hipLaunchKernelGGL((v5_obj_bwd_kernel<float>), dim3(gb, d->num_stage), dim3(256), 0, st, k, all, gout, bal_used, ciou, next, head);
-        hipLaunchKernelGGL((v5_pos_bwd_kernel<float>), dim3(nb_pos, d->num_stage), dim3(256), 0, st, k, all, gout, count, tbox, tidx, next, head);
-    } else {
-        hipLaunchKernelGGL((v5_obj_bwd_kernel<uint16_t>), dim3(gb, d->num_stage), dim3(256), 0, st, k, all, gout, bal_used, ciou, next, head);
-        hipLaunchKernelGGL((v5_pos_bwd_kernel<uint16_t>), dim3(nb_pos, d->num_stage), dim3(256), 0, st, k, all, gout, count, tbox, tidx, next, head);
-    }
+    yh_pred_type(d->pred_is_f32, [&](auto e) {
+        using T = decltype(e);
+        hipLaunchKernelGGL((v5_obj_bwd_kernel<T>), dim3(gb, d->num_stage), dim3(256), 0, st, k, all, gout, bal_used, ciou, next, head);
+        hipLaunchKernelGGL((v5_pos_bwd_kernel<T>), dim3(nb_pos, d->num_stage), dim3(256), 0, st, k, all, gout, count, tbox, tidx, next, head);
+    });
     YH_CHECK_LAUNCH("yh_v5_loss_bwd");
-    return YH_OK;
-}
-
-// ---------------------------------------------------------------- box utilities
-namespace {
-__global__ void iou_matrix_kernel(const float* __restrict__ b1, int n1, const float* __restrict__ b2, int n2,
-                                  float eps_clamp, float* __restrict__ out)
-{
-    long tot = (long)n1 * n2;
-    for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < tot; id += (long)gridDim.x * blockDim.x) {
-        int i = (int)(id / n2), j = (int)(id - (long)i * n2);
-        const float* a = b1 + (size_t)i * 4;
-        const float* b = b2 + (size_t)j * 4;
-        const float a1 = (a[2] - a[0]) * (a[3] - a[1]);
-        const float a2 = (b[2] - b[0]) * (b[3] - b[1]);
-        float w = fminf(a[2], b[2]) - fmaxf(a[0], b[0]);
-        float h = fminf(a[3], b[3]) - fmaxf(a[1], b[1]);
-        if (eps_clamp >= 0.f) { w = fmaxf(w, 0.f); h = fmaxf(h, 0.f); }      // < 0: the evaluators' bbox_iou (trainer/eval_yolov5.py:237-258) clamps nothing
-        const float inter = w * h;
-        float den = a1 + a2 - inter;
-        if (eps_clamp > 0.f) den = fmaxf(den, eps_clamp);      // gpu_iou; 0 -> numba_iou (no clamp, 0/0 = NaN)
-        out[id] = inter / den;
-    }
-}
-
-__global__ void iou_pairwise_kernel(int kind, const float* __restrict__ b1, const float* __restrict__ b2, int n,
-                                    float* __restrict__ out, float* __restrict__ grad)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* a = b1 + (size_t)i * 4;
-    const float* b = b2 + (size_t)i * 4;
-    if (kind == 2) {
-        float g[4];
-        out[i] = ciou_fwd_bwd(a, b, grad ? g : nullptr);
-        if (grad) { grad[i * 4 + 0] = g[0]; grad[i * 4 + 1] = g[1]; grad[i * 4 + 2] = g[2]; grad[i * 4 + 3] = g[3]; }
-        return;
-    }
-    const float eps = 1e-6f;
-    const float a1 = (a[2] - a[0]) * (a[3] - a[1]);
-    const float a2 = (b[2] - b[0]) * (b[3] - b[1]);
-    const float w = fmaxf(fminf(a[2], b[2]) - fmaxf(a[0], b[0]), 0.f);
-    const float h = fmaxf(fminf(a[3], b[3]) - fmaxf(a[1], b[1]), 0.f);
-    const float inter = w * h;
-    const float uni = a1 + a2 - inter;
-    const float iou = inter / fmaxf(uni, eps);
-    const float cw = fmaxf(a[2], b[2]) - fminf(a[0], b[0]);
-    const float chh = fmaxf(a[3], b[3]) - fminf(a[1], b[1]);
-    if (kind == 0) {            // GIoU utils/bbox_tools.py:193-230
-        const float ca = cw * chh;
-        out[i] = iou - fabsf(ca - uni) / fabsf(fmaxf(ca, eps));
-    } else {                    // DIoU :233-283
-        const float cd = cw * cw + chh * chh;
-        const float dx = (a[2] + a[0]) / 2.f - (b[2] + b[0]) / 2.f;
-        const float dy = (a[3] + a[1]) / 2.f - (b[3] + b[1]) / 2.f;
-        float v = iou - (dx * dx + dy * dy) / fmaxf(cd, eps);
-        out[i] = fminf(fmaxf(v, -1.f), 1.f);
-    }
-}
-}  // namespace
-
-extern "C" int yh_iou_matrix(const float* b1, int n1, const float* b2, int n2, float eps_clamp, float* out, yh_stream stream)
-{
-    YH_CHECK_ARG(b1 && b2 && out && n1 >= 0 && n2 >= 0, "yh_iou_matrix: bad args");
-    long tot = (long)n1 * n2;
-    if (tot == 0) return YH_OK;
-    int g = (int)((tot + 255) / 256 > 4096 ? 4096 : (tot + 255) / 256);
-    hipLaunchKernelGGL(iou_matrix_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, b1, n1, b2, n2, eps_clamp, out);
-    YH_CHECK_LAUNCH("yh_iou_matrix");
-    return YH_OK;
-}
-
-extern "C" int yh_iou_pairwise(int kind, const float* b1, const float* b2, int n, float* out, float* grad_b1, yh_stream stream)
-{
-    YH_CHECK_ARG(b1 && b2 && out && n >= 0 && kind >= 0 && kind <= 2, "yh_iou_pairwise: bad args");
-    YH_CHECK_ARG(grad_b1 == nullptr || kind == 2, "yh_iou_pairwise: gradient only for CIoU");
-    if (n == 0) return YH_OK;
-    hipLaunchKernelGGL(iou_pairwise_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, kind, b1, b2, n, out, grad_b1);
-    YH_CHECK_LAUNCH("yh_iou_pairwise");
     return YH_OK;
 }

@@ -28,7 +28,7 @@
 //   2. Rectangular maps.  make_grid (:327-346) swaps the mesh and views (w, h, 2) as (h, w, 2): right for square maps,
 //      scrambled otherwise.  Here x = col + 0.5, y = row + 0.5, stride = img_size0 / H.
 //   3. The NaN branch (print and input(), :68-91) is dropped: NaNs propagate into the result.
-#include "common.h"
+#include "exact_math.h"
 
 namespace {
 
@@ -78,9 +78,6 @@ struct V8K {
 struct StageV { const void* pred; void* gpred; int H, W, ld, off; float stride; };
 struct StagesV { StageV s[MAXS]; };
 
-template <typename T> __device__ __forceinline__ float ldv(const T* p);
-template <> __device__ __forceinline__ float ldv<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float ldv<uint16_t>(const uint16_t* p) { return bf2f(*p); }
 template <typename T> __device__ __forceinline__ void load8(const T* p, float* f);
 template <> __device__ __forceinline__ void load8<float>(const float* p, float* f) {
     const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
@@ -93,8 +90,6 @@ template <> __device__ __forceinline__ void store8<float>(float* p, const float*
     reinterpret_cast<float4*>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
 }
 template <> __device__ __forceinline__ void store8<uint16_t>(uint16_t* p, const float* f) { *reinterpret_cast<uint4*>(p) = pack8(f); }
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // softmax statistics of one side's `reg` logits z[0..reg): mx = max, se = sum exp(z - mx), ex = sum exp(z - mx) * (k + 1).
 // vec: reg % 8 == 0, so that every side starts on a 16-byte boundary of the (16-byte aligned, ld % 8 == 0) cell row
@@ -115,8 +110,8 @@ __device__ __forceinline__ void side_stats(const T* z, int reg, bool vec, float&
             for (int j = 0; j < 8; ++j) { const float e = expf(f[j] - mx); se += e; ex += e * (float)(k0 + j + 1); }
         }
     } else {
-        for (int k = 0; k < reg; ++k) mx = fmaxf(mx, ldv<T>(z + k));
-        for (int k = 0; k < reg; ++k) { const float e = expf(ldv<T>(z + k) - mx); se += e; ex += e * (float)(k + 1); }
+        for (int k = 0; k < reg; ++k) mx = fmaxf(mx, ldf<T>(z + k));
+        for (int k = 0; k < reg; ++k) { const float e = expf(ldf<T>(z + k) - mx); se += e; ex += e * (float)(k + 1); }
     }
 }
 
@@ -142,61 +137,6 @@ __device__ __forceinline__ float ciou_assign(const float* a, const float* b)
     const float v = (float)(4.0 / (3.14159265358979323846 * 3.14159265358979323846)) * (da * da);
     const float alpha = v / fmaxf(1.f - iou + v, eps);
     return iou - (cd / diag + v * alpha);
-}
-
-// gpu_CIoU of xyxy boxes (utils/bbox_tools.py:286-339, eps 1e-9) + gradient w.r.t. b1 with alpha constant: the formulation
-// behind yh_iou_pairwise kind 2 (ciou_fwd_bwd in loss_v5.hip), restated here because that one is private to its file
-__device__ float ciou_loss_term(const float* b1, const float* b2, float* g /*4 or null*/)
-{
-    const float eps = 1e-9f;
-    const float x1 = b1[0], y1 = b1[1], x2 = b1[2], y2 = b1[3];
-    const float X1 = b2[0], Y1 = b2[1], X2 = b2[2], Y2 = b2[3];
-    const float w1 = x2 - x1, h1 = y2 - y1, w2 = X2 - X1, h2 = Y2 - Y1;
-    const float iwr = fminf(x2, X2) - fmaxf(x1, X1), ihr = fminf(y2, Y2) - fmaxf(y1, Y1);
-    const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
-    const float inter = iw * ih;
-    const float union_raw = w1 * h1 + w2 * h2 - inter;
-    const float uni = fmaxf(union_raw, eps);
-    const float iou = inter / uni;
-    const float c_hs = fmaxf(y2, Y2) - fminf(y1, Y1), c_ws = fmaxf(x2, X2) - fminf(x1, X1);
-    const float cd_raw = c_ws * c_ws + c_hs * c_hs;
-    const float ctr_ws = (x1 + x2) / 2.f - (X1 + X2) / 2.f, ctr_hs = (y1 + y2) / 2.f - (Y1 + Y2) / 2.f;
-    const float ctr = ctr_hs * ctr_hs + ctr_ws * ctr_ws;
-    const float kk = (float)(4.0 / (3.14159265358979323846 * 3.14159265358979323846));
-    const float h1c = fmaxf(h1, eps), h2c = fmaxf(h2, eps);
-    const float u1 = w1 / h1c;
-    const float dA = atanf(u1) - atanf(w2 / h2c);
-    const float v = kk * dA * dA;
-    const float alpha = v / fmaxf(1.f - iou + v, eps);
-    const float cd = fmaxf(cd_raw, eps);
-    if (g) {
-        // torch.min / max split the gradient evenly on ties; clamp(min) passes it at >= min
-        auto lt = [](float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); };
-        const float pw_ = (iwr >= 0.f) ? 1.f : 0.f, ph_ = (ihr >= 0.f) ? 1.f : 0.f;
-        const float diw[4] = {-pw_ * lt(X1, x1), 0.f, pw_ * lt(x2, X2), 0.f};
-        const float dih[4] = {0.f, -ph_ * lt(Y1, y1), 0.f, ph_ * lt(y2, Y2)};
-        const float dw1[4] = {-1.f, 0.f, 1.f, 0.f};
-        const float dh1[4] = {0.f, -1.f, 0.f, 1.f};
-        const float dcw[4] = {-lt(x1, X1), 0.f, lt(X2, x2), 0.f};
-        const float dch[4] = {0.f, -lt(y1, Y1), 0.f, lt(Y2, y2)};
-        const float dcx[4] = {0.5f, 0.f, 0.5f, 0.f};
-        const float dcy[4] = {0.f, 0.5f, 0.f, 0.5f};
-        const float du_dw = 1.f / h1c;
-        const float du_dh = (h1 >= eps) ? -w1 / (h1c * h1c) : 0.f;
-        const float datan = 1.f / (1.f + u1 * u1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float dinter = ih * diw[i] + iw * dih[i];
-            const float dunion = (union_raw >= eps) ? (dw1[i] * h1 + w1 * dh1[i] - dinter) : 0.f;
-            const float diou = (dinter * uni - inter * dunion) / (uni * uni);
-            const float dcd = (cd_raw >= eps) ? (2.f * c_ws * dcw[i] + 2.f * c_hs * dch[i]) : 0.f;
-            const float dctr = 2.f * ctr_ws * dcx[i] + 2.f * ctr_hs * dcy[i];
-            const float dterm = (dctr * cd - ctr * dcd) / (cd * cd);
-            const float dv = 2.f * kk * dA * datan * (du_dw * dw1[i] + du_dh * dh1[i]);
-            g[i] = diou - dterm - alpha * dv;
-        }
-    }
-    return iou - (ctr / cd + v * alpha);
 }
 
 // The class term of one logit: BCE-with-logits with pos_weight times the focal factor of focal_loss_factor (:348-368), and
@@ -234,7 +174,7 @@ __device__ __forceinline__ bool pair_eval(const yh_v8loss_desc& d, const float* 
     const float4 q = *reinterpret_cast<const float4*>(pbox);
     const float pb[4] = {q.x * stride, q.y * stride, q.z * stride, q.w * stride};
     iou = fmaxf(ciou_assign(tb, pb), 0.f);
-    metric = powf(iou, d.beta) * powf(sigm(ldv<T>(row + 4 * d.reg + cls)), d.alpha);
+    metric = powf(iou, d.beta) * powf(sigm(ldf<T>(row + 4 * d.reg + cls)), d.alpha);
     return true;
 }
 
@@ -453,7 +393,7 @@ __global__ __launch_bounds__(256) void v8_loss_fwd_kernel(const V8K p, const Sta
                 const float4 q = *reinterpret_cast<const float4*>(pbox + gc * 4);
                 const float pb[4] = {q.x, q.y, q.z, q.w};
                 const float tbs[4] = {tg[0] / st.stride, tg[1] / st.stride, tg[2] / st.stride, tg[3] / st.stride};
-                const float ci = ciou_loss_term(pb, tbs, nullptr);
+                const float ci = ciou_fwd_bwd(pb, tbs, nullptr);
                 float tt[4], dfl = 0.f;
                 dfl_target(tbs, gx, gy, d.reg, tt);
 #pragma unroll
@@ -464,7 +404,7 @@ __global__ __launch_bounds__(256) void v8_loss_fwd_kernel(const V8K p, const Sta
                     const float lse = mx + logf(se);
                     const int tl = (int)tt[side];
                     const float wl = (float)(tl + 1) - tt[side], wr = 1.f - wl;
-                    dfl += (lse - ldv<T>(z + tl)) * wl + (lse - ldv<T>(z + tl + 1)) * wr;
+                    dfl += (lse - ldf<T>(z + tl)) * wl + (lse - ldf<T>(z + tl + 1)) * wr;
                 }
                 acc[1] += (double)((1.f - ci) * norm);
                 acc[2] += (double)(dfl / 4.f * norm);
@@ -473,14 +413,8 @@ __global__ __launch_bounds__(256) void v8_loss_fwd_kernel(const V8K p, const Sta
             }
         }
     }
-#pragma unroll
-    for (int k = 0; k < NKIND; ++k) {
-        const double a = wave_sum_d(acc[k]);
-        if ((threadIdx.x & 63) == 0) sred[k][threadIdx.x >> 6] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < NKIND)
-        part[((size_t)threadIdx.x * MAXS + blockIdx.y) * NB + blockIdx.x] = sred[threadIdx.x][0] + sred[threadIdx.x][1] + sred[threadIdx.x][2] + sred[threadIdx.x][3];
+    block_partials(acc, sred);
+    if (threadIdx.x < NKIND) part[((size_t)threadIdx.x * MAXS + blockIdx.y) * NB + blockIdx.x] = block_total(sred[threadIdx.x]);
 }
 
 // one block of NKIND waves: wave k sums kind k over the stages' partials in a fixed order
@@ -558,7 +492,7 @@ __global__ __launch_bounds__(256) void v8_loss_bwd_kernel(const V8K p, const Sta
             }
             const float tbs[4] = {tg[0] / st.stride, tg[1] / st.stride, tg[2] / st.stride, tg[3] / st.stride};
             float gci[4], tt[4];
-            ciou_loss_term(pb, tbs, gci);
+            ciou_fwd_bwd(pb, tbs, gci);
             dfl_target(tbs, gx, gy, reg, tt);
             // d(iou term) / d(expected distance) per side: the box moves against t and l, with b and r
             const float kin = -ki * norm;
@@ -651,17 +585,13 @@ extern "C" int yh_v8_loss_fwd(const yh_v8loss_desc* d, const void* const* preds,
     const dim3 g_pre(blocks_for(cmax * 4, 8192), d->num_stage), g_asg(d->maxbox, d->B), g_loss(NB, d->num_stage);
     const int g_res = blocks_for((long)d->B * k.L.N, 8192);
     const size_t lds = (size_t)d->topk * 256 * sizeof(unsigned long long);
-    if (d->pred_is_f32) {
-        hipLaunchKernelGGL((v8_pre_kernel<float>), g_pre, dim3(256), 0, st, k, all, wsb, sv);
-        hipLaunchKernelGGL((v8_assign_kernel<float>), g_asg, dim3(256), lds, st, k, all, targets, wsb, sv);
-        hipLaunchKernelGGL((v8_resolve_kernel<float>), dim3(g_res), dim3(256), 0, st, k, all, targets, wsb, sv);
-        hipLaunchKernelGGL((v8_loss_fwd_kernel<float>), g_loss, dim3(256), 0, st, k, all, targets, wsb, sv, part);
-    } else {
-        hipLaunchKernelGGL((v8_pre_kernel<uint16_t>), g_pre, dim3(256), 0, st, k, all, wsb, sv);
-        hipLaunchKernelGGL((v8_assign_kernel<uint16_t>), g_asg, dim3(256), lds, st, k, all, targets, wsb, sv);
-        hipLaunchKernelGGL((v8_resolve_kernel<uint16_t>), dim3(g_res), dim3(256), 0, st, k, all, targets, wsb, sv);
-        hipLaunchKernelGGL((v8_loss_fwd_kernel<uint16_t>), g_loss, dim3(256), 0, st, k, all, targets, wsb, sv, part);
-    }
+    yh_pred_type(d->pred_is_f32, [&](auto e) {
+        using T = decltype(e);
+        hipLaunchKernelGGL((v8_pre_kernel<T>), g_pre, dim3(256), 0, st, k, all, wsb, sv);
+        hipLaunchKernelGGL((v8_assign_kernel<T>), g_asg, dim3(256), lds, st, k, all, targets, wsb, sv);
+        hipLaunchKernelGGL((v8_resolve_kernel<T>), dim3(g_res), dim3(256), 0, st, k, all, targets, wsb, sv);
+        hipLaunchKernelGGL((v8_loss_fwd_kernel<T>), g_loss, dim3(256), 0, st, k, all, targets, wsb, sv, part);
+    });
     hipLaunchKernelGGL(v8_finalize_kernel, dim3(1), dim3(64 * NKIND), 0, st, k, part, sv, result);
     YH_CHECK_LAUNCH("yh_v8_loss_fwd");
     return YH_OK;
@@ -684,8 +614,9 @@ extern "C" int yh_v8_loss_bwd(const yh_v8loss_desc* d, const void* const* preds,
     long chmax = 1;
     for (int s = 0; s < d->num_stage; ++s) { const long c = (long)d->B * d->H[s] * d->W[s] * (d->ldp[s] / 8); if (c > chmax) chmax = c; }
     const dim3 grid(blocks_for(chmax, 8192), d->num_stage);
-    if (d->pred_is_f32) hipLaunchKernelGGL((v8_loss_bwd_kernel<float>), grid, dim3(256), 0, st, k, all, targets, (const unsigned char*)saved, gout);
-    else                hipLaunchKernelGGL((v8_loss_bwd_kernel<uint16_t>), grid, dim3(256), 0, st, k, all, targets, (const unsigned char*)saved, gout);
+    yh_pred_type(d->pred_is_f32, [&](auto e) {
+        hipLaunchKernelGGL((v8_loss_bwd_kernel<decltype(e)>), grid, dim3(256), 0, st, k, all, targets, (const unsigned char*)saved, gout);
+    });
     YH_CHECK_LAUNCH("yh_v8_loss_bwd");
     return YH_OK;
 }

@@ -14,7 +14,7 @@
 //            not detached there, :92,:150).
 // Reference quirk kept: the class/objectness part of the assignment cost is a constant
 // (`cls_cost_const`, computed by the host with the reference's expression on zero logits, :111-147).
-#include "common.h"
+#include "exact_math.h"
 
 namespace {
 
@@ -69,15 +69,6 @@ struct XK {
     yh_yolox_desc d;
     XLayout L;
 };
-
-template <typename T> __device__ __forceinline__ float ldx(const T* p);
-template <> __device__ __forceinline__ float ldx<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float ldx<uint16_t>(const uint16_t* p) { return bf2f(*p); }
-template <typename T> __device__ __forceinline__ void stx(T* p, float v);
-template <> __device__ __forceinline__ void stx<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void stx<uint16_t>(uint16_t* p, float v) { *p = f2bf(v); }
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // gpu_iou of two xyxy boxes (utils/bbox_tools.py:164-190)
 __device__ __forceinline__ float iou_xyxy(float ax0, float ay0, float ax1, float ay1, float bx0, float by0, float bx1, float by1) {
@@ -252,8 +243,8 @@ __global__ __launch_bounds__(1024) void yolox_assign_kernel(const XK p, const St
                 const int cell = cand[y];
                 const T* row = pred + (size_t)cell * st.ld;
                 const float gxc = (float)(cell % st.W), gyc = (float)(cell / st.W);
-                const float px = (ldx<T>(row) + gxc) * stride, py = (ldx<T>(row + 1) + gyc) * stride;
-                const float pw = expf(ldx<T>(row + 2)) * stride, ph = expf(ldx<T>(row + 3)) * stride;
+                const float px = (ldf<T>(row) + gxc) * stride, py = (ldf<T>(row + 1) + gyc) * stride;
+                const float pw = expf(ldf<T>(row + 2)) * stride, ph = expf(ldf<T>(row + 3)) * stride;
                 qx0[j] = px - pw / 2.f; qy0[j] = py - ph / 2.f; qx1[j] = px + pw / 2.f; qy1[j] = py + ph / 2.f;
                 qxy[j] = (cell % st.W) | ((cell / st.W) << 16);
             } else {
@@ -440,8 +431,8 @@ __global__ __launch_bounds__(1024) void yolox_assign_kernel(const XK p, const St
         const int cell = cand[y];
         const T* row = pred + (size_t)cell * st.ld;
         const float gxc = (float)(cell % st.W), gyc = (float)(cell / st.W);
-        const float px = (ldx<T>(row) + gxc) * stride, py = (ldx<T>(row + 1) + gyc) * stride;
-        const float pw = expf(ldx<T>(row + 2)) * stride, ph = expf(ldx<T>(row + 3)) * stride;
+        const float px = (ldf<T>(row) + gxc) * stride, py = (ldf<T>(row + 1) + gyc) * stride;
+        const float pw = expf(ldf<T>(row + 2)) * stride, ph = expf(ldf<T>(row + 3)) * stride;
         const float x = gt[g][0], yy = gt[g][1], w = gt[g][2], h = gt[g][3];
         const float iou = iou_xyxy(x - w / 2.f, yy - h / 2.f, x + w / 2.f, yy + h / 2.f, px - pw / 2.f, py - ph / 2.f, px + pw / 2.f, py + ph / 2.f);
         const float cx = (gxc + 0.5f) * stride, cy = (gyc + 0.5f) * stride;
@@ -599,26 +590,6 @@ __device__ Dual matched_iou_dual(const float* pb, const float* tb)
     return inter / dclampmin(a1 + a2 - inter, 1e-9f);
 }
 
-__device__ __forceinline__ float bce_logits(float x, float t, float pw, float* dx, float* dt) {
-    const float lw = 1.0f + (pw - 1.0f) * t;
-    const float sp = log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.0f);      // softplus(-x) = -log(sigmoid(x))
-    const float sg = sigm(x);
-    if (dx) *dx = (1.0f - t) - lw * (1.0f - sg);
-    if (dt) *dt = -x + (pw - 1.0f) * sp;                              // d/dt [(1-t)x + (1+(pw-1)t) sp]
-    return (1.0f - t) * x + lw * sp;
-}
-__device__ __forceinline__ float focal_factor(float x, float t, float gamma, float alpha, float* dx, float* dt) {
-    const float pr = sigm(x);
-    const float acc = t * pr + (1.0f - t) * (1.0f - pr);
-    const float om = 1.0f - acc;
-    const float gf = powf(om, gamma);
-    const float af = t * alpha + (1.0f - t) * (1.0f - alpha);
-    const float dgf_dom = om > 0.f ? gamma * powf(om, gamma - 1.0f) : 0.f;
-    if (dx) *dx = dgf_dom * (-(2.0f * t - 1.0f) * pr * (1.0f - pr)) * af;
-    if (dt) *dt = dgf_dom * (-(2.0f * pr - 1.0f)) * af + gf * (2.0f * alpha - 1.0f);
-    return gf * af;
-}
-
 // ------------------------------------------------------------------------------------------------
 template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void yolox_fg_kernel(const XK p, const StagesX sts, const float* __restrict__ targets,
@@ -639,7 +610,7 @@ __global__ __launch_bounds__(256) void yolox_fg_kernel(const XK p, const StagesX
     (void)bal_used;
     const T* pred = reinterpret_cast<const T*>(st.pred);
     T* gp = reinterpret_cast<T*>(st.gpred);
-    double a_iou = 0.0, a_l1 = 0.0, a_cls = 0.0;
+    double acc[3] = {0.0, 0.0, 0.0};          // iou, l1, class
     float kiou = 0.f, kl1 = 0.f, kcls = 0.f;
     if (BWD) {
         const float nf = (float)(nfg_stage[s] > 1 ? nfg_stage[s] : 1);
@@ -661,7 +632,7 @@ __global__ __launch_bounds__(256) void yolox_fg_kernel(const XK p, const StagesX
             const T* row = pred + roff;
             float lg[4];
             {
-                float mine = (sub < 4) ? ldx<T>(row + sub) : 0.f;
+                float mine = (sub < 4) ? ldf<T>(row + sub) : 0.f;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) lg[i] = __shfl(mine, i, 16);
             }
@@ -674,7 +645,7 @@ __global__ __launch_bounds__(256) void yolox_fg_kernel(const XK p, const StagesX
             // class loss over this lane's classes; target = onehot * smooth * matched_iou
             float csum = 0.f, dmiou = 0.f;
             for (int e = 5 + sub; e < E; e += 16) {
-                const float x = ldx<T>(row + e);
+                const float x = ldf<T>(row + e);
                 const bool hot = (e - 5 == tcls);
                 const float tt = hot ? d.cls_smooth * miou : 0.f;
                 float dx, dtb, fdx = 0.f, fdt = 0.f, f = 1.f;
@@ -682,14 +653,14 @@ __global__ __launch_bounds__(256) void yolox_fg_kernel(const XK p, const StagesX
                 if (d.use_focal) f = focal_factor(x, tt, d.focal_gamma, d.focal_alpha, &fdx, &fdt);
                 csum += l * f;
                 if (BWD) {
-                    stx<T>(gp + roff + e, kcls * (dx * f + l * fdx) / (float)nc);
+                    stf<T>(gp + roff + e, kcls * (dx * f + l * fdx) / (float)nc);
                     if (hot) dmiou = kcls * (dtb * f + l * fdt) * d.cls_smooth / (float)nc;
                 }
             }
 #pragma unroll
             for (int o = 8; o > 0; o >>= 1) { csum += __shfl_xor(csum, o, 16); dmiou += __shfl_xor(dmiou, o, 16); }
             if (sub == 0) {
-                a_iou += (double)il.v; a_l1 += (double)l1; a_cls += (double)(csum / (float)nc);
+                acc[0] += (double)il.v; acc[1] += (double)l1; acc[2] += (double)(csum / (float)nc);
                 if (BWD) {
                     const Dual mi = matched_iou_dual(pb, tb);       // class target carries gradient into the box (:150)
                     float gb[4];
@@ -704,18 +675,16 @@ __global__ __launch_bounds__(256) void yolox_fg_kernel(const XK p, const StagesX
                         }
                     }
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) stx<T>(gp + roff + i, gl[i]);
+                    for (int i = 0; i < 4; ++i) stf<T>(gp + roff + i, gl[i]);
                 }
             }
         }
     }
     if (!BWD) {
-        a_iou = wave_sum_d(a_iou); a_l1 = wave_sum_d(a_l1); a_cls = wave_sum_d(a_cls);
-        if ((t & 63) == 0) { sred[0][t >> 6] = a_iou; sred[1][t >> 6] = a_l1; sred[2][t >> 6] = a_cls; }
-        __syncthreads();
+        block_partials(acc, sred);
         if (t == 0) {
             for (int k = 0; k < 3; ++k)
-                part[((size_t)s * 4 + k) * PARTS + blockIdx.y * gridDim.x + blockIdx.x] = sred[k][0] + sred[k][1] + sred[k][2] + sred[k][3];
+                part[((size_t)s * 4 + k) * PARTS + blockIdx.y * gridDim.x + blockIdx.x] = block_total(sred[k]);
         }
     }
 }
@@ -725,24 +694,22 @@ __global__ __launch_bounds__(256) void yolox_obj_fwd_kernel(const XK p, const St
                                                             double* __restrict__ part)
 {
     const StageX st = sts.s[blockIdx.y];          // one launch for all stages
-    __shared__ double sred[4];
+    __shared__ double sred[1][4];
     const yh_yolox_desc& d = p.d;
     const int s = st.s, n = st.H * st.W;
     const long tot = (long)d.B * n;
     const int32_t* cellmap = reinterpret_cast<const int32_t*>(svb + p.L.cellmap) + p.L.cell_off[s];
     const T* pred = reinterpret_cast<const T*>(st.pred);
-    double acc = 0.0;
+    double acc[1] = {0.0};
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long)gridDim.x * blockDim.x) {
-        const float x = ldx<T>(pred + (size_t)i * st.ld + 4);
+        const float x = ldf<T>(pred + (size_t)i * st.ld + 4);
         const float tt = cellmap[i] >= 0 ? 1.f : 0.f;
         float l = bce_logits(x, tt, d.cof_pos_weight, nullptr, nullptr);
         if (d.use_focal) l *= focal_factor(x, tt, d.focal_gamma, d.focal_alpha, nullptr, nullptr);
-        acc += (double)l;
+        acc[0] += (double)l;
     }
-    acc = wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[((size_t)s * 4 + 3) * PARTS + blockIdx.x] = sred[0] + sred[1] + sred[2] + sred[3];
+    block_partials(acc, sred);
+    if (threadIdx.x == 0) part[((size_t)s * 4 + 3) * PARTS + blockIdx.x] = block_total(sred[0]);
 }
 
 __global__ __launch_bounds__(1024) void yolox_finalize_kernel(const XK p, const double* __restrict__ part, int nb_fg, int nb_obj,
@@ -835,7 +802,7 @@ __global__ __launch_bounds__(256) void yolox_obj_bwd_kernel(const XK p, const St
             const long cell = cell0 + t;
             float gv = 0.f;
             if (cell < ncell) {
-                const float x = ldx<T>(pred + (size_t)cell * st.ld + 4);
+                const float x = ldf<T>(pred + (size_t)cell * st.ld + 4);
                 const float tt = cellmap[cell] >= 0 ? 1.f : 0.f;
                 float dx, fdx = 0.f, f = 1.f;
                 const float l = bce_logits(x, tt, d.cof_pos_weight, &dx, nullptr);
@@ -877,6 +844,16 @@ int check_xdesc(const yh_yolox_desc* d, const char* who) {
     return YH_OK;
 }
 
+// the four stage slots of a launch; slots past num_stage repeat stage 0 and are never indexed (the grids span num_stage)
+void fill_stages(const yh_yolox_desc* d, const void* const* preds, void* const* gpreds, StagesX& all) {
+    for (int s = 0; s < MAXS; ++s) {
+        const int q = s < d->num_stage ? s : 0;
+        StageX& sg = all.s[s];
+        sg.pred = preds[q]; sg.gpred = gpreds ? gpreds[q] : nullptr; sg.s = q; sg.H = d->H[q]; sg.W = d->W[q]; sg.ld = d->ldp[q];
+        sg.stride = d->img_size0 / (float)d->H[q];
+    }
+}
+
 }  // namespace
 
 extern "C" size_t yh_yolox_saved_bytes(const yh_yolox_desc* d) { return d ? make_xlayout(*d).total : 0; }
@@ -904,24 +881,16 @@ extern "C" int yh_yolox_loss_fwd(const yh_yolox_desc* d, const void* const* pred
     double* part = reinterpret_cast<double*>(wsb + k.L.w_part);
     const int nb_fg = 256, nb_obj = 512;
     const dim3 fg_grid(4, nb_fg / 4);              // x: shares of an image's foreground list, y: images
+    for (int s = 0; s < d->num_stage; ++s) YH_CHECK_ARG(preds[s] && yh_aligned16(preds[s]), "yh_yolox_loss_fwd: preds[%d] null/unaligned", s);
     StagesX all;
-    for (int s = 0; s < d->num_stage; ++s) {
-        YH_CHECK_ARG(preds[s] && yh_aligned16(preds[s]), "yh_yolox_loss_fwd: preds[%d] null/unaligned", s);
-        StageX& sg = all.s[s];
-        sg.pred = preds[s]; sg.gpred = nullptr; sg.s = s; sg.H = d->H[s]; sg.W = d->W[s]; sg.ld = d->ldp[s];
-        sg.stride = d->img_size0 / (float)d->H[s];
-    }
-    if (d->pred_is_f32) hipLaunchKernelGGL((yolox_assign_kernel<float>), dim3(d->B, d->num_stage), dim3(1024), 0, st, k, all, targets_xywh, wsb, sv);
-    else                hipLaunchKernelGGL((yolox_assign_kernel<uint16_t>), dim3(d->B, d->num_stage), dim3(1024), 0, st, k, all, targets_xywh, wsb, sv);
-    for (int s = d->num_stage; s < MAXS; ++s) all.s[s] = all.s[0];
+    fill_stages(d, preds, nullptr, all);
     const dim3 fg_grid3(fg_grid.x, fg_grid.y, d->num_stage);
-    if (d->pred_is_f32) {
-        hipLaunchKernelGGL((yolox_fg_kernel<float, false>), fg_grid3, dim3(256), 0, st, k, all, targets_xywh, sv, part, (const float*)nullptr);
-        hipLaunchKernelGGL((yolox_obj_fwd_kernel<float>), dim3(nb_obj, d->num_stage), dim3(256), 0, st, k, all, sv, part);
-    } else {
-        hipLaunchKernelGGL((yolox_fg_kernel<uint16_t, false>), fg_grid3, dim3(256), 0, st, k, all, targets_xywh, sv, part, (const float*)nullptr);
-        hipLaunchKernelGGL((yolox_obj_fwd_kernel<uint16_t>), dim3(nb_obj, d->num_stage), dim3(256), 0, st, k, all, sv, part);
-    }
+    yh_pred_type(d->pred_is_f32, [&](auto e) {
+        using T = decltype(e);
+        hipLaunchKernelGGL((yolox_assign_kernel<T>), dim3(d->B, d->num_stage), dim3(1024), 0, st, k, all, targets_xywh, wsb, sv);
+        hipLaunchKernelGGL((yolox_fg_kernel<T, false>), fg_grid3, dim3(256), 0, st, k, all, targets_xywh, sv, part, (const float*)nullptr);
+        hipLaunchKernelGGL((yolox_obj_fwd_kernel<T>), dim3(nb_obj, d->num_stage), dim3(256), 0, st, k, all, sv, part);
+    });
     hipLaunchKernelGGL(yolox_finalize_kernel, dim3(1), dim3(1024), 0, st, k, part, nb_fg, nb_obj, targets_xywh, sv, balances, result);
     YH_CHECK_LAUNCH("yh_yolox_loss_fwd");
     return YH_OK;
@@ -939,23 +908,18 @@ extern "C" int yh_yolox_loss_bwd(const yh_yolox_desc* d, const void* const* pred
     StagesX all;
     long ntile_max = 1;
     for (int s = 0; s < d->num_stage; ++s) YH_CHECK_ARG(preds[s] && gpreds[s] && yh_aligned16(gpreds[s]), "yh_yolox_loss_bwd: stage %d pointers null/unaligned", s);
-    for (int s = 0; s < MAXS; ++s) {
-        const int q = s < d->num_stage ? s : 0;
-        StageX& sg = all.s[s];
-        sg.pred = preds[q]; sg.gpred = gpreds[q]; sg.s = q; sg.H = d->H[q]; sg.W = d->W[q]; sg.ld = d->ldp[q];
-        sg.stride = d->img_size0 / (float)d->H[q];
-        const long ntile = ((long)d->B * sg.H * sg.W + 255) / 256;
-        if (s < d->num_stage && ntile > ntile_max) ntile_max = ntile;
+    fill_stages(d, preds, gpreds, all);
+    for (int s = 0; s < d->num_stage; ++s) {
+        const long ntile = ((long)d->B * d->H[s] * d->W[s] + 255) / 256;
+        if (ntile > ntile_max) ntile_max = ntile;
     }
     const int gb = (int)(ntile_max > 4096 ? 4096 : ntile_max);
     // objectness pass (writes every stage's whole gradient tensor), then the foreground cells fill their channels: two launches
-    if (d->pred_is_f32) {
-        hipLaunchKernelGGL((yolox_obj_bwd_kernel<float>), dim3(gb, d->num_stage), dim3(256), 0, st, k, all, sv, gout);
-        hipLaunchKernelGGL((yolox_fg_kernel<float, true>), dim3(4, 64, d->num_stage), dim3(256), 0, st, k, all, targets_xywh, sv, (double*)nullptr, gout);
-    } else {
-        hipLaunchKernelGGL((yolox_obj_bwd_kernel<uint16_t>), dim3(gb, d->num_stage), dim3(256), 0, st, k, all, sv, gout);
-        hipLaunchKernelGGL((yolox_fg_kernel<uint16_t, true>), dim3(4, 64, d->num_stage), dim3(256), 0, st, k, all, targets_xywh, sv, (double*)nullptr, gout);
-    }
+    yh_pred_type(d->pred_is_f32, [&](auto e) {
+        using T = decltype(e);
+        hipLaunchKernelGGL((yolox_obj_bwd_kernel<T>), dim3(gb, d->num_stage), dim3(256), 0, st, k, all, sv, gout);
+        hipLaunchKernelGGL((yolox_fg_kernel<T, true>), dim3(4, 64, d->num_stage), dim3(256), 0, st, k, all, targets_xywh, sv, (double*)nullptr, gout);
+    });
     YH_CHECK_LAUNCH("yh_yolox_loss_bwd");
     return YH_OK;
 }

@@ -15,17 +15,11 @@
 //                   the "merge" filter of eval_yolov5.py:306-315.  Wave-level arg-max via shuffles.
 // All comparisons are in fp32 with the reference's operation order (compiled with -ffp-contract=off).
 #include <float.h>
-#include "common.h"
+#include "exact_math.h"
 
 namespace {
 
 constexpr int MAXS = 4;
-
-template <typename T> __device__ __forceinline__ float ldv(const T* p);
-template <> __device__ __forceinline__ float ldv<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float ldv<uint16_t>(const uint16_t* p) { return bf2f(*p); }
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // view of one pass: how its centre-format boxes map back to the original image, and whether its candidates follow the rows
 // already in the table.  {1, 0, .., .., 0} is yh_decode_filter: x * 1.0f is x, and the table starts at row 0.
@@ -68,15 +62,15 @@ template <typename T>
 __device__ __forceinline__ void decode_box(const DecK& k, const T* row, int s, int a, int y, int x, float* box) {
     const float st = k.d.stride[s];
     if (k.d.yolox) {          // eval_yolox.py:140-143
-        box[0] = (ldv<T>(row + 0) + (float)x) * st;
-        box[1] = (ldv<T>(row + 1) + (float)y) * st;
-        box[2] = expf(ldv<T>(row + 2)) * st;
-        box[3] = expf(ldv<T>(row + 3)) * st;
+        box[0] = (ldf<T>(row + 0) + (float)x) * st;
+        box[1] = (ldf<T>(row + 1) + (float)y) * st;
+        box[2] = expf(ldf<T>(row + 2)) * st;
+        box[3] = expf(ldf<T>(row + 3)) * st;
     } else {                  // eval_yolov5.py:203-205
         const float aw = k.d.anchors[s][a][0] / st, ah = k.d.anchors[s][a][1] / st;
-        box[0] = (sigm(ldv<T>(row + 0)) * 2.f - 0.5f + (float)x) * st;
-        box[1] = (sigm(ldv<T>(row + 1)) * 2.f - 0.5f + (float)y) * st;
-        const float tw = sigm(ldv<T>(row + 2)) * 2.f, th = sigm(ldv<T>(row + 3)) * 2.f;
+        box[0] = (sigm(ldf<T>(row + 0)) * 2.f - 0.5f + (float)x) * st;
+        box[1] = (sigm(ldf<T>(row + 1)) * 2.f - 0.5f + (float)y) * st;
+        const float tw = sigm(ldf<T>(row + 2)) * 2.f, th = sigm(ldf<T>(row + 3)) * 2.f;
         box[2] = tw * tw * aw * st;
         box[3] = th * th * ah * st;
     }
@@ -101,7 +95,7 @@ __global__ void decode_full_kernel(const DecK k, float* __restrict__ out)
             decode_box<T>(k, row, s, a, y, x, box);
             v = box[e];
         } else {
-            v = sigm(ldv<T>(row + e));
+            v = sigm(ldf<T>(row + e));
         }
         out[id] = v;
     }
@@ -113,12 +107,12 @@ __device__ __forceinline__ bool eval_pred(const DecK& k, const ViewK& v, const T
                                           float cls_thr, float* box, float& conf, int& cls)
 {
     const int nc = k.d.num_class;
-    const float obj = sigm(ldv<T>(row + 4));
+    const float obj = sigm(ldf<T>(row + 4));
     bool pass = k.d.yolox ? true : (obj >= conf_thr);                 // eval_yolov5.py:266
     if (!pass) return false;
     float best = -INFINITY, best_raw = -INFINITY;
     for (int c = 0; c < nc; ++c) {
-        const float pc = sigm(ldv<T>(row + 5 + c));
+        const float pc = sigm(ldf<T>(row + 5 + c));
         const float sc = pc * obj;                                // x[:, 5:] *= x[:, 4:5]
         if (sc > best) { best = sc; cls = c; }                    // first maximum
         if (pc > best_raw) best_raw = pc;
@@ -635,8 +629,9 @@ extern "C" int yh_decode_full(const yh_decode_desc* d, const void* const* preds,
     YH_CHECK_ARG(out != nullptr, "yh_decode_full: null output");
     long tot = (long)d->B * k.ntot * (5 + d->num_class);
     int g = (int)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256);
-    if (d->pred_is_f32) hipLaunchKernelGGL((decode_full_kernel<float>), dim3(g), dim3(256), 0, (hipStream_t)stream, k, out);
-    else                hipLaunchKernelGGL((decode_full_kernel<uint16_t>), dim3(g), dim3(256), 0, (hipStream_t)stream, k, out);
+    yh_pred_type(d->pred_is_f32, [&](auto e) {
+        hipLaunchKernelGGL((decode_full_kernel<decltype(e)>), dim3(g), dim3(256), 0, (hipStream_t)stream, k, out);
+    });
     YH_CHECK_LAUNCH("yh_decode_full");
     return YH_OK;
 }
@@ -669,15 +664,12 @@ int decode_filter_launch(const yh_decode_desc* d, const void* const* preds, cons
         YH_CHECK_ARG(sm <= 160 * 1024, "%s: prediction rows of %d elements do not fit the LDS tile", who, ldmax);
         const dim3 grid(nchunks, d->B);
         char label[64];
-        if (d->pred_is_f32) {
-            static YhDevOnce attr;
-            yh_lds_limit(attr, {{(const void*)decode_scan_kernel<float>, 160 * 1024}});
-            hipLaunchKernelGGL((decode_scan_kernel<float>), grid, dim3(256), sm, (hipStream_t)stream, k, v, conf_thr, cls_thr, stage, counts, nkeys);
-        } else {
-            static YhDevOnce attr;
-            yh_lds_limit(attr, {{(const void*)decode_scan_kernel<uint16_t>, 160 * 1024}});
-            hipLaunchKernelGGL((decode_scan_kernel<uint16_t>), grid, dim3(256), sm, (hipStream_t)stream, k, v, conf_thr, cls_thr, stage, counts, nkeys);
-        }
+        yh_pred_type(d->pred_is_f32, [&](auto e) {
+            using T = decltype(e);
+            static YhDevOnce attr;          // one per element type: the attribute belongs to the instantiation
+            yh_lds_limit(attr, {{(const void*)decode_scan_kernel<T>, 160 * 1024}});
+            hipLaunchKernelGGL((decode_scan_kernel<T>), grid, dim3(256), sm, (hipStream_t)stream, k, v, conf_thr, cls_thr, stage, counts, nkeys);
+        });
         snprintf(label, sizeof(label), "%s(scan)", who);
         YH_CHECK_LAUNCH(label);
         hipLaunchKernelGGL(decode_gather_kernel, dim3(d->B), dim3(1024), 0, (hipStream_t)stream, stage, counts, nkeys, cand, ncand, cap, v.append);
@@ -685,8 +677,9 @@ int decode_filter_launch(const yh_decode_desc* d, const void* const* preds, cons
         YH_CHECK_LAUNCH(label);
         return YH_OK;
     }
-    if (d->pred_is_f32) hipLaunchKernelGGL((decode_filter_kernel<float>), dim3(d->B), dim3(1024), 0, (hipStream_t)stream, k, v, conf_thr, cls_thr, cand, ncand, cap);
-    else                hipLaunchKernelGGL((decode_filter_kernel<uint16_t>), dim3(d->B), dim3(1024), 0, (hipStream_t)stream, k, v, conf_thr, cls_thr, cand, ncand, cap);
+    yh_pred_type(d->pred_is_f32, [&](auto e) {
+        hipLaunchKernelGGL((decode_filter_kernel<decltype(e)>), dim3(d->B), dim3(1024), 0, (hipStream_t)stream, k, v, conf_thr, cls_thr, cand, ncand, cap);
+    });
     YH_CHECK_LAUNCH(who);
     return YH_OK;
 }

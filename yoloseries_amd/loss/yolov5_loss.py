@@ -12,106 +12,28 @@ import torch
 
 from .. import _lib
 from .._lib import V5LossDesc, check, lib
+from ._base import BalancedLossBase, canon_heads
 
 __all__ = ["YOLOV5Loss"]
 
 
-def _canon(p):
-    """Return (tensor_in_cell_major_layout, ld, was_view). Accepts (B, Ctot, h, w)."""
-    B, Ct, h, w = p.shape
-    st = p.stride()
-    if p.dtype in (torch.bfloat16, torch.float32) and st[1] == 1 and st[3] % 8 == 0 and st[3] >= Ct \
-            and st[2] == w * st[3] and st[0] == h * w * st[3] and p.data_ptr() % 16 == 0:
-        return p, st[3], True
-    ld = ((Ct + 7) // 8) * 8
-    dt = p.dtype if p.dtype in (torch.bfloat16, torch.float32) else torch.float32
-    buf = torch.zeros(B, h, w, ld, dtype=dt, device=p.device)
-    buf[..., :Ct] = p.detach().permute(0, 2, 3, 1)
-    return buf.as_strided((B, Ct, h, w), (h * w * ld, 1, w * ld, ld)), ld, False
-
-
-class _V5LossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, owner, targets, *preds):
-        desc, canon, lds = owner._make_desc(preds, targets)
-        L = lib()
-        dev = targets.device
-        saved = torch.empty(L.yh_v5loss_saved_bytes(C.byref(desc)), dtype=torch.uint8, device=dev)
-        tptr = targets.data_ptr()
-        ws = owner._workspace(L.yh_v5loss_ws_bytes(C.byref(desc)), dev)
-        result = torch.empty(8, dtype=torch.float32, device=dev)
-        ptrs = (C.c_void_p * 4)(*[c.data_ptr() for c in canon], *([None] * (4 - len(canon))))
-        check(L.yh_v5_loss_fwd(C.byref(desc), ptrs, tptr, owner._balances.data_ptr(), result.data_ptr(),
-                               saved.data_ptr(), ws.data_ptr(), _lib.stream_ptr()), "yh_v5_loss_fwd")
-        ctx.owner, ctx.desc, ctx.canon, ctx.saved = owner, desc, canon, saved
-        ctx.in_meta = [(p.shape, p.dtype, p.stride()) for p in preds]
-        ctx.mark_non_differentiable(result)
-        return result[0:1].clone(), result
-
-    @staticmethod
-    def backward(ctx, gtot, _gres):
-        L = lib()
-        desc, canon = ctx.desc, ctx.canon
-        gout = gtot.to(torch.float32).contiguous()
-        gbufs = []
-        for c in canon:
-            B, Ct, h, w = c.shape
-            ld = c.stride(3)
-            gbufs.append(torch.empty(B, h, w, ld, dtype=c.dtype, device=c.device))
-        ptrs = (C.c_void_p * 4)(*[c.data_ptr() for c in canon], *([None] * (4 - len(canon))))
-        gptrs = (C.c_void_p * 4)(*[g.data_ptr() for g in gbufs], *([None] * (4 - len(canon))))
-        ws = ctx.owner._workspace(L.yh_v5loss_ws_bytes(C.byref(desc)), gout.device)
-        check(L.yh_v5_loss_bwd(C.byref(desc), ptrs, gout.data_ptr(), ctx.saved.data_ptr(), gptrs, ws.data_ptr(),
-                               _lib.stream_ptr()), "yh_v5_loss_bwd")
-        outs = []
-        for g, c, (shape, dtype, stride) in zip(gbufs, canon, ctx.in_meta):
-            B, Ct, h, w = c.shape
-            ld = c.stride(3)
-            v = g.as_strided((B, Ct, h, w), (h * w * ld, 1, w * ld, ld))
-            outs.append(v if v.dtype == dtype else v.to(dtype))
-        return (None, None, *outs)
-
-
-class YOLOV5Loss:
+class YOLOV5Loss(BalancedLossBase):
+    _SAVED_BYTES, _WS_BYTES = "yh_v5loss_saved_bytes", "yh_v5loss_ws_bytes"
+    _SIZE_ATTR = "input_img_size"
+    _KEEP_LAST = False          # no debug reader of the last call's state: nothing keeps its `saved` buffer alive
+    _MAX_GT = None
 
     def __init__(self, anchors, hyp, stage_num=3):
         """:param anchors: tensor (3, 3, 2) in pixels; :param hyp: flat config dict (config/config.py:14-20)"""
+        super().__init__(stage_num)
         self.anchors = anchors
         self.hyp = hyp
         self.device = hyp['device']
         self.input_img_size = hyp['input_img_size']
         self.stage_num = stage_num
-        self._init_balances = [4., 1., 0.4] if stage_num == 3 else [4., 1., 0.4, 0.1]
-        self._balances = None
-        self._ws = None
         self._anchors_host = [[[float(v) for v in a] for a in st] for st in anchors.detach().cpu().tolist()]
 
-    # ---- state -----------------------------------------------------------------------------
-    def set_input_img_size(self, hw):
-        """The size [h, w] of the images behind the next predictions (multi-scale training: the size of the step).  Everything a
-        call derives from the size -- target normalisation, the anchors' grid scale, in __call__ and assign -- goes into a
-        descriptor built from this attribute when the call runs (nothing of an earlier size is kept); a NEW list is stored, so `hyp['input_img_size']`, which the evaluators share, keeps
-        the configured value.  (The reference normalises by the configured size whatever the step's: DESIGN.md section 4.)"""
-        self.input_img_size = [int(hw[0]), int(hw[1])]
-
-    @property
-    def balances(self):
-        if self._balances is None:
-            return list(self._init_balances)
-        return self._balances.cpu().tolist()[:self.stage_num]
-
-    @balances.setter
-    def balances(self, v):
-        self._init_balances = [float(x) for x in v]
-        if self._balances is not None:
-            self._balances[:len(v)] = torch.tensor(self._init_balances, dtype=torch.float64, device=self._balances.device)
-
-    def _workspace(self, nbytes, dev):
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return self._ws
-
-    def _make_desc(self, preds, targets, canon_given=None):
+    def _make_desc(self, preds, targets):
         hyp = self.hyp
         d = V5LossDesc()
         d.B, d.maxbox = targets.shape[0], targets.shape[1]
@@ -119,12 +41,10 @@ class YOLOV5Loss:
         d.num_anchor = len(self._anchors_host[0])
         d.num_stage = len(preds)
         d.img_size0, d.img_size1 = float(self.input_img_size[0]), float(self.input_img_size[1])
-        flat = [v for st in self._anchors_host for a in st for v in a]
         for s in range(d.num_stage):
             for a in range(d.num_anchor):
                 d.anchors[(s * 3 + a) * 2 + 0] = self._anchors_host[s][a][0]
                 d.anchors[(s * 3 + a) * 2 + 1] = self._anchors_host[s][a][1]
-        del flat
         d.anchor_thr = float(hyp['anchor_match_thr'])
         d.cls_smooth = float(hyp['class_smooth_factor'])
         d.cls_pos_weight = float(hyp['cls_pos_weight'])
@@ -133,19 +53,21 @@ class YOLOV5Loss:
         d.focal_gamma = float(hyp.get('focal_loss_gamma', 1.5))
         d.focal_alpha = float(hyp.get('focal_loss_alpha', 0.25))
         d.iou_scale, d.cof_scale, d.cls_scale = float(hyp['iou_loss_scale']), float(hyp['cof_loss_scale']), float(hyp['cls_loss_scale'])
-        canon, lds = [], []
-        dts = set()
-        for s, p in enumerate(preds):
-            c, ld, _ = _canon(p)
-            canon.append(c); lds.append(ld); dts.add(c.dtype)
-            d.H[s], d.W[s], d.ldp[s] = p.shape[2], p.shape[3], ld
-            assert p.shape[1] == d.num_anchor * (5 + d.num_class)
-        if len(dts) != 1:
-            canon = [c.float() if c.dtype != torch.float32 else c for c in canon]
-            canon = [_canon(c)[0] for c in canon]
+        canon = canon_heads(preds)
+        for s, c in enumerate(canon):
+            d.H[s], d.W[s], d.ldp[s] = c.shape[2], c.shape[3], c.stride(3)
+            assert c.shape[1] == d.num_anchor * (5 + d.num_class)
         d.pred_is_f32 = int(canon[0].dtype == torch.float32)
         d.targets_xywhn = 0
-        return d, canon, lds
+        return d, canon
+
+    def _fwd(self, L, desc, ptrs, targets, result, saved, ws):
+        check(L.yh_v5_loss_fwd(C.byref(desc), ptrs, targets.data_ptr(), self._balances.data_ptr(), result.data_ptr(),
+                               saved.data_ptr(), ws.data_ptr(), _lib.stream_ptr()), "yh_v5_loss_fwd")
+
+    def _bwd(self, L, desc, ptrs, targets, gout, saved, gptrs, ws):
+        check(L.yh_v5_loss_bwd(C.byref(desc), ptrs, gout.data_ptr(), saved.data_ptr(), gptrs, ws.data_ptr(),
+                               _lib.stream_ptr()), "yh_v5_loss_bwd")
 
     # ---- reference API ---------------------------------------------------------------------
     def __call__(self, stage_preds, targets_batch):
@@ -154,21 +76,9 @@ class YOLOV5Loss:
         assert isinstance(stage_preds, (list, tuple))
         assert isinstance(targets_batch, torch.Tensor), f"targets's type should be torch.Tensor but we got {type(targets_batch)}"
         assert stage_preds[0].size(0) == targets_batch.size(0), "the length of predictions and targets should be the same"
-        if not stage_preds[0].is_cuda:
-            raise _lib.YoloHipError("YOLOV5Loss: predictions must live on an MI355X device (no CPU path in the product)")
-        dev = stage_preds[0].device
-        if self._balances is None or self._balances.device != dev:
-            self._balances = torch.zeros(4, dtype=torch.float64, device=dev)
-            self._balances[:len(self._init_balances)] = torch.tensor(self._init_balances, dtype=torch.float64)
-        targets = targets_batch.detach().to(device=dev, dtype=torch.float32).contiguous()
-        tot, result = _V5LossFn.apply(self, targets, *stage_preds)
-        batch_size = targets_batch.size(0)
-        del batch_size
-        if self.hyp.get('loss_items_on_device', False):
-            # no host sync: the scalars stay on the device (bench / graph-captured training loops)
-            return {'tot_loss': tot, 'iou_loss': result[1], 'cof_loss': result[2], 'cls_loss': result[3], 'tar_nums': result[4]}
-        r = result.tolist()
-        return {'tot_loss': tot, 'iou_loss': r[1], 'cof_loss': r[2], 'cls_loss': r[3], 'tar_nums': int(r[4])}
+        self._guard(stage_preds, targets_batch)
+        tot, result = self._apply(stage_preds, targets_batch)
+        return self._items(tot, result, ('iou_loss', 'cof_loss', 'cls_loss', 'tar_nums'))
 
     def match(self, targets, anchor_stage, fm_shape):
         """Reference signature (loss/yolov5_loss.py:142): targets (A, bn, bbox_num, 7) normalised

@@ -1,5 +1,5 @@
 """Box utilities — mirror of the reference's utils/bbox_tools.py public surface.
-IoU-family functions run on the HIP kernels of csrc/loss_v5.hip (yh_iou_matrix,
+IoU-family functions run on the HIP kernels of csrc/bbox.hip (yh_iou_matrix,
 yh_iou_pairwise); the format conversions are the same one-line tensor expressions
 as the reference (:87-134), evaluated on whatever device the tensor lives on."""
 import numpy as np
