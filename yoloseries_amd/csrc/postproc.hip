@@ -442,6 +442,7 @@ __device__ __forceinline__ float pair_iou(const float4 a, const float4 b, float 
 //      the keep list (stopping at max_keep), and all 16 waves strike out the later candidates those survivors suppress.
 //   At most max_keep chunks are ever resolved (each resolved chunk keeps >= 1 box), two barriers per resolved chunk instead
 //   of three per kept box, and no arg-max scans.  Selection order, tie rule, NaN-IoU and threshold conventions are unchanged.
+// ncand[b] > cap is read as cap.  keep_idx past nkeep[b] is undefined (the merge filter compacts the pick list in place).
 constexpr int NMS_LDS_KEYS = 8192;
 
 __device__ __forceinline__ void bitonic_sort_desc(unsigned long long* keys, int P2, int t)
