@@ -588,6 +588,43 @@ int yh_decode_filter_view(const yh_decode_desc* d, const void* const* preds, con
  * 3 YOLOX multi-label (trainer/eval_yolox.py:218-221: the same among the predictions with obj * max(cls) >= conf_thr). */
 int yh_filter_decoded(const float* dec, int B, int N, int num_class, float conf_thr, float cls_thr, int yolox,
                       float* cand, int32_t* ncand, int cap, yh_stream stream);
+/* YOLOv8 post-processing (trainer/eval_yolov8.py:76-102, :168-196; yoloseries_amd/csrc/postproc_v8.hip).  A head holds, per cell,
+ * 4*reg box logits — sides [t, b, l, r], each softmax(reg logits) . [1, 2, ..., reg] — then num_class class logits; no
+ * objectness, no anchors.  Cells: stages in the order given, row-major inside a stage, N = sum H*W.  Box = (gx - l, gy - t,
+ * gx + r, gy + b) * (img_h / H) with gx = col + 0.5, gy = row + 0.5 (rectangular maps too: the reference's make_grid scrambles
+ * those); scores = sigmoid(class logit), the exact one.  NaN logits are outside the contract.
+ * ldp: elements between consecutive cells of a cell-major view, >= 4*reg + num_class; only the leading 4*reg + num_class
+ * elements of a row are read, rounded up to whole 16-byte pieces where the tensor and ldp are 16-byte aligned. */
+typedef struct yh_v8dec_desc {
+    int32_t B, num_class, num_stage, reg;     /* num_stage 1..4, reg 2..32 */
+    int32_t H[4], W[4], ldp[4];
+    int32_t pred_is_f32;                      /* 1: fp32 heads, 0: bf16 */
+    float   img_h;                            /* height of the network input, pixels */
+} yh_v8dec_desc;
+/* Full decode to (B, N, 4+nc) fp32 [xmin, ymin, xmax, ymax, sigmoid(cls)...], the tensor do_inference returns. */
+int yh_v8_decode_full(const yh_v8dec_desc* d, const void* const* preds, float* out, yh_stream stream);
+/* Fused decode + single-label candidate filter, order preserving: score = max_c sigmoid(x_c) compared on the fp32 sigmoid values,
+ * class = the first index that reaches it, candidate iff score >= cls_thr.  cand [B][cap][6] (xmin, ymin, xmax, ymax, score,
+ * cls), cap a positive multiple of 4: the table yh_nms_batched consumes.  The decoded tensor is never written.
+ *  xf == NULL: the table starts at row 0 and ncand is written, not read.
+ *  xf != NULL: one pass of test-time augmentation (:40-73), APPENDED as yh_decode_filter_view appends (ncand in/out, negative
+ *  counts as 0): every box value times 1.0f / scale (the reciprocal taken once in fp32), then for flip_axis 2
+ *  ymin' = img_h - ymax, ymax' = img_h - ymin, for flip_axis 3 xmin' = img_w - xmax, xmax' = img_w - xmin (xf->img_h / img_w:
+ *  the original image).  {1, 0} with ncand == 0 gives the xf == NULL table bit for bit.
+ *  Rows at or past cap are counted, not stored.
+ *  ws: yh_v8_decode_filter_ws_bytes(d) bytes, 16-byte aligned (staging area [B][chunks of 64 cells][64][6] and counts; nothing is
+ *  sized B*N*(4+nc)): blocks of 64 cells stage their rows through LDS, a second pass per image orders their candidates.
+ *  ws == NULL: one workgroup per image walks the cells (same table bit for bit; for small heads).
+ * YH_EINVAL: null pointers, reg outside 2..32, num_stage outside 1..4, ldp < 4*reg + num_class, bad xf, bad cap, unaligned ws.
+ * All entry points enqueue only: no allocation, no synchronisation. */
+size_t yh_v8_decode_filter_ws_bytes(const yh_v8dec_desc* d);
+int yh_v8_decode_filter(const yh_v8dec_desc* d, const void* const* preds, const yh_view_xform* xf, float cls_thr,
+                        float* cand, int32_t* ncand /* in/out with xf */, int cap, void* ws, yh_stream stream);
+/* The candidate rule on an already decoded (B, N, 4+nc) fp32 tensor, the argument of YOLOV8Evaluator.numba_nms.  multi_label 0: as
+ * yh_v8_decode_filter; 1 (hyp['mutil_label'], :186-189): one row per (cell, class) with value >= cls_thr, in (cell, class) order.
+ * ncand may exceed cap: rows past cap are counted, not stored. */
+int yh_v8_filter_decoded(const float* dec, int B, int N, int num_class, float cls_thr, int multi_label,
+                         float* cand, int32_t* ncand, int cap, yh_stream stream);
 /* Greedy NMS per image on candidate lists, selection order = reference order.
  *  class_aware: add cls*4096 to the box before IoU (hyp['agnostic'] == True in the reference)
  *  thr_inclusive: 1 -> suppress when iou >= thr (numba_nms), 0 -> iou > thr (gpu_nms)

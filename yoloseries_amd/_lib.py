@@ -135,6 +135,13 @@ class ViewXform(C.Structure):
     _fields_ = [("scale", C.c_float), ("flip_axis", C.c_int32), ("img_h", C.c_float), ("img_w", C.c_float)]
 
 
+class V8DecDesc(C.Structure):
+    """yh_v8dec_desc: the YOLOv8 heads of one forward for the decode / filter entry points (csrc/postproc_v8.hip)"""
+    _fields_ = [("B", C.c_int32), ("num_class", C.c_int32), ("num_stage", C.c_int32), ("reg", C.c_int32),
+                ("H", C.c_int32 * 4), ("W", C.c_int32 * 4), ("ldp", C.c_int32 * 4),
+                ("pred_is_f32", C.c_int32), ("img_h", C.c_float)]
+
+
 class AugTile(C.Structure):
     """yh_aug_tile: one pasted image of the virtual mosaic canvas (yh_augment_batch); utils/augment.py TILE_DTYPE is its NumPy form"""
     _fields_ = [("off", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("sx0", C.c_int32), ("sy0", C.c_int32),
@@ -248,6 +255,10 @@ _SIGS = {
     "yh_decode_filter_ws_bytes": (C.c_size_t, [C.POINTER(DecodeDesc)]),
     "yh_decode_filter_view": (_i32, [C.POINTER(DecodeDesc), C.POINTER(_vp), C.POINTER(ViewXform), _f32, _f32, _vp, _vp, _i32, _vp, _vp]),
     "yh_filter_decoded": (_i32, [_vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _i32, _vp]),
+    "yh_v8_decode_full": (_i32, [C.POINTER(V8DecDesc), C.POINTER(_vp), _vp, _vp]),
+    "yh_v8_decode_filter_ws_bytes": (_sz, [C.POINTER(V8DecDesc)]),
+    "yh_v8_decode_filter": (_i32, [C.POINTER(V8DecDesc), C.POINTER(_vp), C.POINTER(ViewXform), _f32, _vp, _vp, _i32, _vp, _vp]),
+    "yh_v8_filter_decoded": (_i32, [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i32, _vp]),
     "yh_exec_op": (_i32, [C.c_char_p, C.POINTER(_i32)]),
     "yh_exec": (_i32, [C.POINTER(Cmd), _i32, C.POINTER(_vp), _i32, C.POINTER(_i32)]),
     "yh_nms_ws_bytes": (_sz, [_i32, _i32]),
