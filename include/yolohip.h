@@ -681,6 +681,29 @@ int yh_val_ap(const float* conf, const int32_t* cls, const uint16_t* tp, const i
               int num_class, int n_thr, const double* xs_ap, int n_ap, const double* xs_pr, int n_pr, double* ap, double* precision,
               double* recall, int32_t* npred, void* ws, yh_stream stream);
 
+/* Weighted box fusion (utils/weighted_fusion_bbox.py, do_wfb of trainer/eval_yolov5.py:44-92) of candidate tables where they lie:
+ * per (image, class), rows by score descending, starting from no cluster, a row joins EVERY cluster whose fused box has fp64 IoU
+ * (cpu_iou: sides clamped at 0, union clipped below at 1e-6) >= iou_thr with it, or founds a new one; the fused boxes are refreshed
+ * after every row (yoloseries_amd/csrc/wbf.hip lists the operation order: fp64 running sums in arrival order, each operation once).
+ *  cand [B][cap][6]: xmin, ymin, xmax, ymax, score, cls.  weight [B][cap]: the row's model weight; <= 0: not a candidate (holes
+ *  anywhere in a table are fine).
+ *  order [B][cap] int32, nvalid [B]: order[b][0 .. nvalid[b]) are the candidate rows of image b — weight > 0, score > 0, 0 <= cls <
+ *  num_class — class ascending, then score descending; the library does not sort.  Entries past nvalid[b] are not read.
+ *  box_mean 0: the reference's box, sum(s_i b_i) / sum(s_i) / N (its np.mean divides by the member count once more); 1: the usual
+ *  weighted box sum(s_i b_i) / sum(s_i).  The fused score is sum(s_i w_i) / sum(w_i) in both.
+ *  out [B][cap][6]: float32 of the fp64 box and score, and the class; rows class ascending, then in the order the clusters were
+ *  founded; nout [B]; rows at or past nout[b] are undefined.  members [B][cap] (may be NULL): N of each output row.
+ *  ws: yh_wbf_ws_bytes(B, cap) bytes, 8-byte aligned.  The state of the first yh_wbf_lds_clusters() clusters of an (image, class)
+ *  lives in LDS, that of the others in ws: the number of clusters is bounded by the number of rows only.
+ * Outside the contract: NaN coordinates or scores; a row below nvalid with cls outside [0, num_class) (its staging slot is never
+ * written).  Neither can make a kernel read or write out of bounds: entries of order and nvalid are clamped.
+ * YH_EINVAL: a NULL pointer (members excepted), non-positive B / cap / num_class, B > 65535, box_mean outside {0, 1}, NaN iou_thr,
+ * an unaligned table.  Two launches (a workgroup per (class, image), then one per image).  Enqueues only: no allocation, no sync. */
+int yh_wbf_lds_clusters(void);
+size_t yh_wbf_ws_bytes(int B, int cap);
+int yh_wbf_batched(const float* cand, const float* weight, const int32_t* order, const int32_t* nvalid, int B, int cap, int num_class,
+                   double iou_thr, int box_mean, float* out, int32_t* nout, int32_t* members, void* ws, yh_stream stream);
+
 /* ------------------------------------------------------------------------
  * Program executor: replay a pre-built list of launches with one call (the engine's forward / backward programs; replaces the
  * host loop over ~700 calls of a train step: train_yolov5.py:327-350 spends that time inside torch's dispatcher instead).

@@ -12,6 +12,8 @@
     there (yh_val_match), a MatchAccumulator keeps the match tables, one copy at the end feeds mAP_v2.from_matches.  Same metric.
   * --device-ap (hyp['device_ap'], implies device_metric): the AP and the precision / recall curves are computed on the device too
     (yh_val_ap through MatchAccumulator.finish_ap); the per-class curves come back instead of the table, mAP_v2.from_curves reads them.
+  * --wfb (hyp['use_tta'] and hyp['wfb']): the passes of the test-time augmentation are merged by weighted box fusion on the device
+    (yh_wbf_batched) instead of NMS; works with the three switches above.  --wfb-box-mean weighted: the usual weighted box.
   Out of scope (SURVEY §8 "OUT OF SCOPE"): image dumps / plots, the auxiliary classifier, pickled box caches.
 
     python val_yolov5.py --img 640 --batch 16 --val-batches 4 [--ckpt checkpoints/yolov5_small_epoch_1.pth]
@@ -172,8 +174,15 @@ def main(argv=None, training_cls=None, default_cfg=None):
                     "GPU (yh_val_match): one match table crosses to the host at the end of the pass instead of every image's rows")
     ap.add_argument("--device-ap", action="store_true", help="with the matching on the GPU (implies --device-metric), compute the AP and "
                     "the precision / recall curves there too (yh_val_ap): the per-class curves cross to the host, not the match table")
+    ap.add_argument("--wfb", action="store_true", help="merge the three test-time-augmentation passes by weighted box fusion on the "
+                    "GPU (yh_wbf_batched) instead of NMS: sets use_tta and wfb; wfb_weights / wfb_iou_threshold / "
+                    "wfb_skip_box_threshold come from the config")
+    ap.add_argument("--wfb-box-mean", choices=("reference", "weighted"), help="fused box: 'reference' divides the weighted box by the "
+                    "cluster's member count once more, as the reference's np.mean does (default); 'weighted' is sum(s b) / sum(s)")
     args = ap.parse_args(argv)
     hyp = Config().get_config(args.cfg)
+    if args.wfb: hyp['use_tta'] = hyp['wfb'] = True                      # noqa: E701
+    if args.wfb_box_mean: hyp['wfb_box_mean'] = args.wfb_box_mean        # noqa: E701
     if args.img: hyp['input_img_size'] = [args.img, args.img]            # noqa: E701
     if args.batch: hyp['batch_size'] = args.batch                        # noqa: E701
     if args.val_batches: hyp['val_batches'] = args.val_batches           # noqa: E701

@@ -267,6 +267,9 @@ _SIGS = {
                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yh_val_ap_ws_bytes": (_sz, [_i32, _i32]),
     "yh_val_ap": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "yh_wbf_lds_clusters": (_i32, []),
+    "yh_wbf_ws_bytes": (_sz, [_i32, _i32]),
+    "yh_wbf_batched": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 

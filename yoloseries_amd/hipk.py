@@ -364,3 +364,54 @@ def ema_update_dev(ema, p, decay_dev):
 
 def ema_advance(counter, decay, ratio, tau):
     check(lib().yh_ema_advance(_p(counter), _p(decay), float(ratio), float(tau), _st()), "yh_ema_advance")
+
+
+WBF_BOX_MEANS = {'reference': 0, 'weighted': 1}
+
+
+def wbf_lds_clusters():
+    """clusters of one (image, class) whose state yh_wbf_batched keeps in LDS; the ones past it live in its workspace"""
+    return int(lib().yh_wbf_lds_clusters())
+
+
+def wbf_order(cand, weight, num_class):
+    """The row order yh_wbf_batched consumes -> (order (B, cap) int32, nvalid (B,) int32): one stable sort of an int64 key per image —
+    non-candidates last, class ascending, the complement of the score's bits (score descending), ties in table order.  A row is a
+    candidate iff weight > 0, score > 0 and 0 <= cls < num_class."""
+    score, cls = cand[:, :, 4], cand[:, :, 5]
+    valid = (weight > 0) & (score > 0) & (cls >= 0) & (cls < num_class)
+    ci = torch.where(valid, cls, torch.zeros_like(cls)).to(torch.int64)
+    bits = score.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    key = torch.where(valid, (ci << 32) | (0xFFFFFFFF - bits), torch.full_like(ci, 1 << 62))
+    return torch.sort(key, dim=1, stable=True)[1].to(torch.int32).contiguous(), valid.sum(dim=1).to(torch.int32)
+
+
+def wbf(cand, weight, iou_thr, box_mean='reference', num_class=None):
+    """Weighted box fusion of candidate tables on the device: wbf_order, the workspace, yh_wbf_batched.
+    cand (B, cap, 6) float32 [xmin, ymin, xmax, ymax, score, cls], weight (B, cap) float32: a row is a candidate iff weight > 0,
+    score > 0 and 0 <= cls < num_class.  num_class None: taken from the table (the one host wait of this function; pass it to stay
+    asynchronous).
+    -> out (B, cap, 6) float32, nout (B,) int32, members (B, cap) int32; rows at or past nout[b] are undefined."""
+    if box_mean not in WBF_BOX_MEANS:
+        raise ValueError(f"wbf: box_mean {box_mean!r} is not one of {sorted(WBF_BOX_MEANS)}")
+    if not cand.is_cuda:
+        raise _lib.YoloHipError("wbf: tensors must live on an MI355X device")
+    cand = cand.to(torch.float32).contiguous()
+    weight = weight.to(device=cand.device, dtype=torch.float32).contiguous()
+    if cand.dim() != 3 or cand.shape[2] != 6 or tuple(weight.shape) != tuple(cand.shape[:2]):
+        raise ValueError(f"wbf: cand {tuple(cand.shape)} / weight {tuple(weight.shape)} are not (B, cap, 6) / (B, cap)")
+    B, cap = cand.shape[0], cand.shape[1]
+    dev = cand.device
+    out = torch.empty(B, max(cap, 1), 6, dtype=torch.float32, device=dev)
+    nout = torch.zeros(B, dtype=torch.int32, device=dev)
+    members = torch.zeros(B, max(cap, 1), dtype=torch.int32, device=dev)
+    if B == 0 or cap == 0:
+        return out, nout, members
+    if num_class is None:
+        cls = cand[:, :, 5]
+        num_class = int(torch.where(weight > 0, cls, torch.zeros_like(cls)).nan_to_num(0.0).clamp(0, 2 ** 20).max().item()) + 1
+    order, nvalid = wbf_order(cand, weight, num_class)
+    ws = torch.empty(max(int(lib().yh_wbf_ws_bytes(B, cap)), 16), dtype=torch.uint8, device=dev)
+    check(lib().yh_wbf_batched(_p(cand), _p(weight), _p(order), _p(nvalid), B, cap, int(num_class), float(iou_thr),
+                               WBF_BOX_MEANS[box_mean], _p(out), _p(nout), _p(members), _p(ws), _st()), "yh_wbf_batched")
+    return out, nout, members

@@ -4,7 +4,8 @@ forward -> decode -> candidate filter -> class-aware greedy NMS -> merge filter 
 the GPU; only the final (n,6) rows per image cross PCIe (the reference copies the whole
 decoded (B, 25200, 85) tensor to the host, :265).  With use_tta each of the three passes is
 decoded and filtered straight from its head tensors into one candidate table
-(_tta_from_heads): no decoded tensor, no concatenation.
+(_tta_from_heads): no decoded tensor, no concatenation.  With use_tta and hyp['wfb'] the table is merged by weighted box fusion
+(csrc/wbf.hip) instead of NMS, where it lies.
 """
 import ctypes as C
 
@@ -132,26 +133,113 @@ class YOLOV5Evaluator:
         self.cls_threshold = hyp['compute_metric_cls_threshold'] if compute_metric else hyp['cls_threshold']
         self.conf_threshold = hyp['compute_metric_conf_threshold'] if compute_metric else hyp['conf_threshold']
         self._anchors_host = anchors.detach().cpu().tolist()
+        self._init_wfb()
+
+    def _init_wfb(self):
+        """hyp['wfb'] (with use_tta only, as in the reference: without it the key is ignored) and its keys, checked once"""
+        from ..hipk import WBF_BOX_MEANS
+        hyp = self.hyp
+        self.wfb = bool(self.use_tta and hyp.get('wfb', False))
+        weights = hyp.get('wfb_weights', None)
+        weights = [1., 1., 1.] if weights is None else list(weights)
+        if len(weights) < len(self._TTA_PASSES):
+            raise ValueError(f"wfb_weights {weights}: test-time augmentation has {len(self._TTA_PASSES)} passes, one weight each")
+        if any(not float(w) > 0 for w in weights):
+            raise ValueError(f"wfb_weights {weights}: every weight must be > 0 (a row with weight <= 0 is no candidate)")
+        self.wfb_weights = [float(w) for w in weights[:len(self._TTA_PASSES)]]
+        if self.wfb and not float(hyp['wfb_skip_box_threshold']) >= 0:          # a fused score divides by the sum of the scores
+            raise ValueError(f"wfb_skip_box_threshold {hyp['wfb_skip_box_threshold']}: must be >= 0 (candidates need a score > 0)")
+        self.wfb_box_mean = hyp.get('wfb_box_mean', 'reference')
+        if self.wfb_box_mean not in WBF_BOX_MEANS:
+            raise ValueError(f"wfb_box_mean {self.wfb_box_mean!r} is not one of {sorted(WBF_BOX_MEANS)}")
 
     # ------------------------------------------------------------------ reference API
     @torch.no_grad()
     def __call__(self, inputs):
         """:param inputs: (b, 3, h, w) -> list (len b) of FloatTensor (n, 6) [xmin, ymin, xmax, ymax, conf, cls] on CPU, or None"""
+        if self.wfb:
+            return self._fusion_rows(*self._wfb_candidates(inputs))
         outs = self._run_nms(*self._candidates(inputs))
         return [torch.from_numpy(x) if x is not None else None for x in outs]
 
     def _candidates(self, inputs):
-        """forward + decode + filter of a batch by the configured path -> candidate table (cand, ncand, B, cap) on the device"""
+        """forward + decode + filter of a batch by the configured path -> candidate table (cand, ncand, B, cap) on the device, for
+        NMS; the table that weighted box fusion merges is _wfb_candidates'"""
         if self.use_tta and self.hyp.get('mutil_label', False):       # through the decoded tensor, like _cand_from_heads
             merge_preds_out, _ = self.test_time_augmentation(inputs)
-            if self.hyp.get("wfb", False):
-                raise NotImplementedError("weighted box fusion is outside the HIP hot path (wfb: false in every shipped config)")
             return self._filter_decoded(merge_preds_out)
         if self.use_tta:
-            if self.hyp.get("wfb", False):
-                raise NotImplementedError("weighted box fusion is outside the HIP hot path (wfb: false in every shipped config)")
             return self._tta_cand(inputs)
         return self._cand_from_heads(self.yolo(inputs))
+
+    # ------------------------------------------------------------------ weighted box fusion (hyp['wfb'] with use_tta)
+    def _wfb_thresholds(self, from_heads):
+        """(conf, cls) thresholds that make the candidate kernels apply do_wfb's rule (eval_yolov5.py:57-74): obj > t, then
+        cls * obj > t, both STRICT, t = wfb_skip_box_threshold as fp32.  The kernels compare in fp32, where v > t is
+        v >= nextafter(t, +inf): the v5 rules test obj >= conf and, single label, best > cls (strict already) or, multi label,
+        cls * obj >= cls."""
+        t = np.float32(self.hyp['wfb_skip_box_threshold'])
+        up = np.nextafter(t, np.float32(np.inf))
+        return float(up), float(up if self.hyp.get('mutil_label', False) else t)
+
+    _WFB_FILTER_MODES = (0, 2)    # do_wfb is the same text in both reference evaluators: the v5 rule of yh_filter_decoded
+
+    def _wfb_decoded(self, preds_out):
+        """per-pass decoded tensors -> (cand (B, cap, 6), weight (B, cap)): each pass filtered by do_wfb's rule (yh_filter_decoded),
+        the tables side by side, weight 0 on the unused tail of each"""
+        if len(preds_out) > len(self.wfb_weights):
+            raise ValueError(f"do_wfb: {len(preds_out)} passes, {len(self.wfb_weights)} weights")
+        mode = self._WFB_FILTER_MODES[1 if self.hyp.get('mutil_label', False) else 0]
+        cands, weights = [], []
+        for p, w in zip(preds_out, self.wfb_weights):
+            cand, ncand, B, cap = self._filter_decoded(p, self._wfb_thresholds(False), mode)
+            cands.append(cand)
+            weights.append((torch.arange(cap, device=cand.device)[None, :] < ncand[:, None]).to(torch.float32) * w)
+        return torch.cat(cands, dim=1), torch.cat(weights, dim=1)
+
+    def _wfb_candidates(self, inputs):
+        """forward + decode + do_wfb's filter of the three passes -> (cand (B, cap, 6), weight (B, cap)) on the device"""
+        if self.hyp.get('mutil_label', False):                        # one row per (prediction, class): through the decoded tensors
+            return self._wfb_decoded(self.test_time_augmentation(inputs)[1])
+        cand, _ncand, _B, _cap, weight = self._tta_table(inputs, self._wfb_thresholds(True), self.wfb_weights)
+        return cand, weight
+
+    def _fuse_device(self, cand, weight):
+        """yh_wbf_batched on a candidate table -> (out (B, cap, 6), nout (B,)) on the device; nothing is copied or awaited"""
+        from ..hipk import wbf
+        out, nout, _members = wbf(cand, weight, float(self.hyp['wfb_iou_threshold']), self.wfb_box_mean, num_class=self.num_class)
+        return out, nout
+
+    def _fusion_rows(self, cand, weight):
+        """_fuse_device + the copy of its table to the host -> list (len B) of FloatTensor (n, 6), class ascending then in the order
+        the clusters were founded, or None"""
+        out, nout = self._fuse_device(cand, weight)
+        self.last_ncand = (weight > 0).sum(dim=1).cpu().tolist()
+        n_h = nout.cpu().tolist()
+        out_h = out.cpu()
+        return [None if n_h[b] == 0 else out_h[b, :n_h[b]].clone() for b in range(len(n_h))]
+
+    @torch.no_grad()
+    def do_wfb(self, preds_out):
+        """"weighted fusion bbox" (trainer/eval_yolov5.py:44-92): the decoded tensors of the passes [(bs, X, 5+nc), ...] -> per
+        image None, or the reference's nesting: one list per class present (ascending) of that class's fused rows, arrays
+        [xmin, ymin, xmax, ymax, score, class] — the rows __call__ returns, from the same kernel"""
+        rows = self._fusion_rows(*self._wfb_decoded(list(preds_out)))
+        nested = []
+        for r in rows:
+            if r is None:
+                nested.append(None)
+                continue
+            r = r.numpy()
+            nested.append([[x for x in r[r[:, 5] == c]] for c in np.unique(r[:, 5])])
+        return nested
+
+    def _detections_device(self, inputs):
+        """the forward and the merge of a batch by the configured path -> (det (B, K, 6), n (B,)) on the device: the NMS table, or
+        with use_tta and hyp['wfb'] the fusion table"""
+        if self.wfb:
+            return self._fuse_device(*self._wfb_candidates(inputs))
+        return self._nms_device(*self._candidates(inputs))
 
     def _desc(self, stage_preds):
         d = DecodeDesc()
@@ -214,17 +302,16 @@ class YOLOV5Evaluator:
     # ------------------------------------------------------------------ metric on the device
     @torch.no_grad()
     def evaluate_matches(self, inputs, ann, info, gt_hist=None):
-        """The forward, filter and NMS of __call__, then yh_val_match on the NMS table where it lies: the detections in the ORIGINAL
+        """The forward, filter and NMS (or fusion) of __call__, then yh_val_match on that table where it lies: the detections in the ORIGINAL
         frame and their true-positive matches against `ann`, as device tensors — nothing is copied to the host or awaited.
         :param ann: (B, maxbox, >= 5) [xmin, ymin, xmax, ymax, cls, ...] in the letterboxed frame, cls < 0 = padding (the collate format)
         :param info: (B, 5) float32 [scale, pad_top, pad_left, org_h, org_w], or the batch's list of resize_info dicts
         :param gt_hist: (num_class,) int32 device tensor to accumulate the ground-truth classes into (MatchAccumulator.gt_hist)
         :return: dict of box (B, K, 4), conf (B, K), cls (B, K) int32, iou (B, K), gt_idx (B, K) int32, tp (B, K) int16 (bit k: IoU
                  threshold k of mAP_v2, read it as uint16), nrow (B,) int32, gt_hist; rows at or past nrow[b] are undefined"""
-        cand, ncand, B, cap = self._candidates(inputs)
-        det, nkeep = self._nms_device(cand, ncand, B, cap)
+        det, nkeep = self._detections_device(inputs)
         dev = det.device
-        K = det.shape[1]
+        B, K = det.shape[0], det.shape[1]
         info = info_tensor(info).to(dev, non_blocking=True)
         ann = ann.to(device=dev, dtype=torch.float32)
         if ann.dim() != 3 or ann.shape[0] != B or ann.shape[2] < 5 or tuple(info.shape) != (B, 5):
@@ -285,11 +372,18 @@ class YOLOV5Evaluator:
         un-flipped straight from its heads (yh_decode_filter_view) and appended to one candidate table, in the order of the
         concatenation, before the next forward overwrites the engine's head buffers; one NMS over the table.  Same rows as
         numba_nms(test_time_augmentation(inputs)[0]), bit for bit."""
+        return self._tta_table(inputs, (self.conf_threshold, self.cls_threshold))[:4]
+
+    def _tta_table(self, inputs, thresholds, pass_weights=None):
+        """_tta_cand's table under the given (conf, cls) thresholds -> (cand, ncand, B, cap, weight); with pass_weights, weight
+        (B, cap) holds the weight of the pass that wrote each row (0 on the unused tail), set on the device from the counts before
+        and after the pass"""
+        conf_thr, cls_thr = thresholds
         img_h, img_w = inputs.size(2), inputs.size(3)
         cap = None
         while True:
-            cand, n_all = None, 0
-            for s, f in self._TTA_PASSES:
+            cand, n_all, weight = None, 0, None
+            for k, (s, f) in enumerate(self._TTA_PASSES):
                 img = inputs.flip(dims=(f,)) if f else inputs
                 img = self.scale_img(img, s)
                 d, canon, ptrs = self._view_desc(self.yolo(img), img)
@@ -301,21 +395,30 @@ class YOLOV5Evaluator:
                         cap = min(((3 * n + 3) // 4) * 4, self._TTA_FIRST_CAP)
                     cand = torch.empty(B, cap, 6, dtype=torch.float32, device=dev)
                     ncand = torch.zeros(B, dtype=torch.int32, device=dev)
+                    if pass_weights is not None:
+                        weight = torch.zeros(B, cap, dtype=torch.float32, device=dev)
+                        col = torch.arange(cap, device=dev)[None, :]
+                if weight is not None:
+                    before = ncand.clone()
                 xf = ViewXform(s, f or 0, img_h, img_w)
-                check(lib().yh_decode_filter_view(C.byref(d), ptrs, C.byref(xf), float(self.conf_threshold), float(self.cls_threshold),
+                check(lib().yh_decode_filter_view(C.byref(d), ptrs, C.byref(xf), float(conf_thr), float(cls_thr),
                                                   cand.data_ptr(), ncand.data_ptr(), cap, _decode_ws(self, d, dev), _lib.stream_ptr()),
                       "yh_decode_filter_view")
+                if weight is not None:
+                    weight.masked_fill_((col >= before[:, None]) & (col < ncand[:, None]), float(pass_weights[k]))
             if cap >= n_all or int(ncand.max().item()) <= cap:
                 break
             cap = ((n_all + 3) // 4) * 4                  # one row per prediction of the three passes: cannot overflow
-        return cand, ncand, B, cap
+        return cand, ncand, B, cap, weight
 
     _FILTER_MODES = (0, 2)        # yh_filter_decoded mode of the single-label / hyp['mutil_label'] candidate rule (:266-286)
 
-    def _filter_decoded(self, preds_out):
+    def _filter_decoded(self, preds_out, thresholds=None, mode=None):
         """decoded (bs, N, 5+nc) -> candidate tables (bs, cap, 6) [xmin, ymin, xmax, ymax, conf, cls] + counts, on the device:
         obj >= conf threshold, cls * obj, arg-max > cls threshold or — hyp['mutil_label'] — one candidate per (prediction, class)
-        in np.nonzero order (:266-286; yh_filter_decoded)"""
+        in np.nonzero order (:266-286; yh_filter_decoded).  thresholds / mode: (conf, cls) and the yh_filter_decoded mode in place
+        of the evaluator's own (the fusion path)"""
+        conf_thr, cls_thr = thresholds or (self.conf_threshold, self.cls_threshold)
         p = preds_out.detach().to(torch.float32).contiguous()
         if not p.is_cuda:
             p = p.to(self.device if str(self.device).startswith("cuda") else "cuda:0")
@@ -323,11 +426,12 @@ class YOLOV5Evaluator:
         assert E == 5 + self.num_class
         cap = ((n + 3) // 4) * 4
         multi = bool(self.hyp.get('mutil_label', False))
-        mode = self._FILTER_MODES[1 if multi else 0]
+        if mode is None:
+            mode = self._FILTER_MODES[1 if multi else 0]
         while True:
             cand = torch.empty(B, cap, 6, dtype=torch.float32, device=p.device)
             ncand = torch.zeros(B, dtype=torch.int32, device=p.device)
-            check(lib().yh_filter_decoded(p.data_ptr(), B, n, self.num_class, float(self.conf_threshold), float(self.cls_threshold), mode,
+            check(lib().yh_filter_decoded(p.data_ptr(), B, n, self.num_class, float(conf_thr), float(cls_thr), mode,
                                           cand.data_ptr(), ncand.data_ptr(), cap, _lib.stream_ptr()), "yh_filter_decoded")
             most = int(ncand.max().item()) if multi else 0          # multi-label: up to num_class candidates per prediction
             if most <= cap:

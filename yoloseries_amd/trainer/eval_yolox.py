@@ -1,6 +1,7 @@
 """YOLOXEvaluator — mirror of trainer/eval_yolox.py:11-259 over csrc/postproc.hip (yolox decode / filter variants)."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from .. import _lib
@@ -27,6 +28,7 @@ class YOLOXEvaluator(YOLOV5Evaluator):
         self.cls_threshold = hyp['compute_metric_cls_threshold'] if compute_metric else hyp['cls_threshold']
         self.conf_threshold = hyp['compute_metric_conf_threshold'] if compute_metric else hyp['conf_threshold']
         self._yolox = 1
+        self._init_wfb()
 
     def _stage_list(self, stage_preds):
         vals = list(stage_preds.values()) if isinstance(stage_preds, dict) else list(stage_preds)
@@ -90,6 +92,17 @@ class YOLOXEvaluator(YOLOV5Evaluator):
         if self.use_tta:
             return self._tta_cand(inputs)                             # inherited; strides per pass from _view_desc
         return self._cand_from_heads(self.yolo(inputs), inputs.size(2))
+
+    def _wfb_thresholds(self, from_heads):
+        """do_wfb is the same text in the reference's YOLOX evaluator, the v5 candidate rule (obj > t, cls * obj > t) included.
+        On decoded tensors yh_filter_decoded runs in its v5 modes (inherited).  From the heads the kernel applies THIS evaluator's
+        rule, obj * max(cls) >= conf and max(cls * obj) >= cls: with both thresholds at nextafter(t, +inf) that is the v5 rule,
+        because obj * max(cls) and max(cls * obj) are the same fp32 number (one correctly rounded product, monotone in cls) and
+        cls <= 1 (a sigmoid) makes cls * obj > t imply obj > t."""
+        if not from_heads:
+            return super()._wfb_thresholds(False)
+        up = np.nextafter(np.float32(self.hyp['wfb_skip_box_threshold']), np.float32(np.inf))
+        return float(up), float(up)
 
     def _nms_from_heads(self, stage_preds, img_h=None):
         return self._run_nms(*self._cand_from_heads(stage_preds, img_h))
