@@ -472,6 +472,35 @@ int yh_v5_loss_bwd(const yh_v5loss_desc* d, const void* const* preds, const floa
                    const void* saved, void* const* gpreds, void* ws, yh_stream stream);
 
 /* ------------------------------------------------------------------------ *
+ * YOLOv7 loss (loss/yolov7_loss.py:17-402): the YOLOv5 anchor / neighbour match (yh_v5_assign) yields a candidate LIST per
+ * stage, a SimOTA dynamic-k assignment over the candidates of each (image, stage) keeps some of them, and CIoU, class BCE
+ * and all-cell objectness BCE run over what is kept.  Same head tensors as the YOLOv5 loss.
+ * ------------------------------------------------------------------------ */
+typedef struct yh_v7loss_desc {
+    yh_v5loss_desc v5;            /* every field as in the YOLOv5 loss, except: cls_smooth is not read (the class targets are
+                                     smooth_bce()'s 0.95 / 0.05) and targets_xywhn must be 0                               */
+    int32_t topk;                 /* hyp['topk'], 1..24                                                                    */
+    int32_t use_iou_as_tar_cof;   /* objectness target of a matched cell: 1 clamp(ciou, 0), 0 the constant 1.0             */
+} yh_v7loss_desc;
+/* At most 128 valid rows (class id >= 0) per image, the contract of the YOLOX loss: the CALLER guarantees it (YOLOV7Loss counts
+ * them whenever maxbox > 128 and raises before any launch); later valid rows of an image would be left out of the SimOTA step.
+ * An (image, stage) therefore has at most 5 * num_anchor * min(maxbox, 128) candidates.  With cap = 5 * num_anchor * B * maxbox,
+ * ws holds 76 bytes and saved 48 bytes per stage and cap row, plus 4 bytes per cell in saved: nothing grows with
+ * maxbox^2 * B or with cells * maxbox.                                                                                   */
+size_t yh_v7loss_ws_bytes(const yh_v7loss_desc* d);
+size_t yh_v7loss_saved_bytes(const yh_v7loss_desc* d);
+/* preds / targets / balances / saved as in yh_v5_loss_fwd.  result fp32[8]: tot, iou, cof, cls, tar_nums, 0, 0, 0     */
+int yh_v7_loss_fwd(const yh_v7loss_desc* d, const void* const* preds, const float* targets,
+                   double* balances, float* result, void* saved, void* ws, yh_stream stream);
+/* gpreds[s]: same geometry/dtype as preds[s], fully overwritten.  gout: device pointer to d(loss)/d(tot).               */
+int yh_v7_loss_bwd(const yh_v7loss_desc* d, const void* const* preds, const float* gout,
+                   const void* saved, void* const* gpreds, void* ws, yh_stream stream);
+/* (debug / tests) the matched rows of the forward call that wrote `saved`, in candidate order:
+ * count[4] int32 (matched rows per stage), rows[num_stage][cap][5] int32 (img, anchor, gy, gx, target row inside the image's
+ * maxbox rows); rows past a stage's count are -1.  Both are device buffers.                                             */
+int yh_v7_matches(const yh_v7loss_desc* d, const void* saved, int32_t* count, int32_t* rows, yh_stream stream);
+
+/* ------------------------------------------------------------------------ *
  * YOLOX loss with SimOTA assignment (loss/yolox_loss.py:11-458)
  * ------------------------------------------------------------------------ */
 typedef struct yh_yolox_desc {

@@ -118,6 +118,10 @@ class V8LossDesc(C.Structure):
     ]
 
 
+class V7LossDesc(C.Structure):
+    _fields_ = [("v5", V5LossDesc), ("topk", C.c_int32), ("use_iou_as_tar_cof", C.c_int32)]
+
+
 class DecodeDesc(C.Structure):
     _fields_ = [
         ("B", C.c_int32), ("num_class", C.c_int32), ("num_anchor", C.c_int32), ("num_stage", C.c_int32),
@@ -248,6 +252,11 @@ _SIGS = {
     "yh_v8loss_layout": (_i32, [C.POINTER(V8LossDesc), _vp]),
     "yh_v8_loss_fwd": (_i32, [C.POINTER(V8LossDesc), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
     "yh_v8_loss_bwd": (_i32, [C.POINTER(V8LossDesc), C.POINTER(_vp), _vp, _vp, _vp, C.POINTER(_vp), _vp, _vp]),
+    "yh_v7loss_ws_bytes": (_sz, [C.POINTER(V7LossDesc)]),
+    "yh_v7loss_saved_bytes": (_sz, [C.POINTER(V7LossDesc)]),
+    "yh_v7_loss_fwd": (_i32, [C.POINTER(V7LossDesc), C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "yh_v7_loss_bwd": (_i32, [C.POINTER(V7LossDesc), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), _vp, _vp]),
+    "yh_v7_matches": (_i32, [C.POINTER(V7LossDesc), _vp, _vp, _vp, _vp]),
     "yh_iou_matrix": (_i32, [_vp, _i32, _vp, _i32, _f32, _vp, _vp]),
     "yh_iou_pairwise": (_i32, [_i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "yh_decode_full": (_i32, [C.POINTER(DecodeDesc), C.POINTER(_vp), _vp, _vp]),
